@@ -15,11 +15,21 @@ without a torchrun environment starts N worker processes itself (before anything
 with the same environment torchrun would give them.  The only exchange is the final size/ratio
 reduction (RCCL all-reduce over xGMI) and the max-over-ranks time.
 
-The dominant kernel's roofline is measured live with HIP events on the launch stream; the CPU
-baseline is the oracle (the libzstd-backed C restatement of the reference's C5 path) on one host
-thread over a bounded sample, plus an all-cores leg (reads sharded over the box's CPU share).
+The dominant kernel's roofline is measured live with HIP events on the launch stream, inside the
+timed steps.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--samples S] [--global-reads G]
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+result line.  `--full` adds what takes runs of its own: the side measurements (STREAM copy,
+PCIe-inclusive, per-chunk plugin calls, batched POD5 host path) and the CPU baselines -- the oracle
+(the libzstd-backed C restatement of the reference's C5 path) on one host thread over a bounded
+sample, plus an all-cores leg (reads sharded over the box's CPU share).
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as DIR/<name>.npy: the blob
+sizes and the encode / decode status of every read, and the blob bytes and decoded samples of a
+fixed, seeded sample of the reads (dump_outputs).
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                  [--reads R] [--samples S] [--global-reads G]
 """
 from __future__ import annotations
 
@@ -64,12 +74,16 @@ def parse(argv=None):
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                    help="nccl (= RCCL) for one process per GPU; gloo lets several ranks share one GPU (rehearsal)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the side measurements (STREAM copy, PCIe-inclusive, per-chunk plugin, POD5 host "
+                        "batch) and the CPU baselines; a plain run times the steps only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs (rank 0) as DIR/<name>.npy")
     p.add_argument("--cpu-sample-reads", type=int, default=600)
     p.add_argument("--cpu-threads", type=int, default=0, help="all-cores CPU leg threads (0 = the box's CPU share)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     p.add_argument("--no-side", action="store_true",
-                   help="skip the STREAM-copy, PCIe-inclusive and per-chunk side measurements (profiling runs: "
-                        "the kernel statistics then hold only the bench batch's launches)")
+                   help="--full without the STREAM-copy, PCIe-inclusive and per-chunk side measurements")
     p.add_argument("--traffic-json", default=None,
                    help="PMC traffic summary (default: profiles/ file of this workload, TRAFFIC_FILES)")
     # the other BASELINE configs; the default run is configs[1]
@@ -80,7 +94,12 @@ def parse(argv=None):
     p.add_argument("--decode-only", action="store_true", help="configs[4]: time the decode of the batch only")
     p.add_argument("--compare-vbz", action="store_true",
                    help="configs[2]: also encode the batch with VBZ (--VBZ) and report the size ratio")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
 
 
 # ---- multi-process launch (no GPU in the parent) ------------------------------------------------
@@ -458,6 +477,55 @@ def load_traffic(path, R, S, dominant, workload):
     return tj.get(dominant), os.path.relpath(path, ROOT)
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------
+DUMP_STATUS_READS = 500_000     # reads whose size / status are written (24 bytes each)
+DUMP_SAMPLE_BYTES = 40_000_000  # float32 bytes of the sampled blobs and decoded samples
+DUMP_SAMPLES_PER_READ = 1 << 20
+
+
+def dump_picks(seed: int, nb: int, S: int):
+    """(reads whose size and status are written, reads whose blob and samples are written): every
+    read of the batch up to DUMP_STATUS_READS, else a seeded sample of them; and a seeded sample of
+    as many reads as DUMP_SAMPLE_BYTES holds at 4 bytes per blob byte (the 2 * S + 26 bound) and per
+    decoded sample.  Both depend on the arguments only, never on what was computed."""
+    import numpy as np
+
+    L = min(S, DUMP_SAMPLES_PER_READ)
+    k = min(nb, max(1, DUMP_SAMPLE_BYTES // (4 * (L + 2 * L + 26))))
+    perm = np.random.default_rng(seed).permutation(nb)
+    return np.sort(perm[:DUMP_STATUS_READS]), np.sort(perm[:k]), L
+
+
+def dump_outputs(dirpath, seed, nb, S, enc, boffs, decoded, offs, dec_status):
+    """What a caller of the timed path received in the last timed step (its last batch of nb reads),
+    as float32 / float64 .npy files, below 64 MB in all:
+      reads, sizes (float64), encode_status, decode_status (float32)   per read of `reads`
+      sample_reads, sample_blob_sizes (float64)                        per sampled read
+      sample_blobs (float32): the sampled reads' blob bytes, one read after the other
+      sample_decoded (float32, [reads, samples]): the sampled reads' decoded samples
+    (blobs and samples of more than DUMP_SAMPLES_PER_READ samples per read are cut to their head)."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    reads, picks, L = dump_picks(seed, nb, S)
+    sizes = enc.sizes[:nb].cpu().numpy().astype(np.int64)
+    np.save(os.path.join(dirpath, "reads.npy"), reads.astype(np.float64))
+    np.save(os.path.join(dirpath, "sizes.npy"), sizes[reads].astype(np.float64))
+    np.save(os.path.join(dirpath, "encode_status.npy"), enc.status[:nb].cpu().numpy()[reads].astype(np.float32))
+    np.save(os.path.join(dirpath, "decode_status.npy"), dec_status[:nb].cpu().numpy()[reads].astype(np.float32))
+    bo = boffs[:nb].cpu().numpy()
+    so = offs[:nb].cpu().numpy()
+    kept = np.clip(sizes[picks], 0, 2 * L + 26)
+    blobs = [enc.blobs[int(bo[r]):int(bo[r]) + int(n)].cpu().numpy() for r, n in zip(picks, kept)]
+    dec = [decoded[int(so[r]):int(so[r]) + L].cpu().numpy() for r in picks]
+    np.save(os.path.join(dirpath, "sample_reads.npy"), picks.astype(np.float64))
+    np.save(os.path.join(dirpath, "sample_blob_sizes.npy"), kept.astype(np.float64))
+    np.save(os.path.join(dirpath, "sample_blobs.npy"),
+            np.concatenate(blobs).astype(np.float32) if blobs else np.zeros(0, np.float32))
+    np.save(os.path.join(dirpath, "sample_decoded.npy"),
+            np.stack(dec).astype(np.float32) if dec else np.zeros((0, L), np.float32))
+
+
 # ---- one rank ---------------------------------------------------------------------------------
 def run_rank(args, rank, world, local, codec, torch, dist, device="cuda", cuda=True):
     """The timed body of one rank: generate this rank's reads (resident), warm up, time exactly
@@ -506,8 +574,8 @@ def run_rank(args, rank, world, local, codec, torch, dist, device="cuda", cuda=T
                                     out_caps=caps[:nb], stream=codec.stream)
 
     def decode(nb, sizes):
-        codec.decompress_batch(blobs, boffs[:nb], sizes, counts[:nb], out=decoded, out_offsets=offs[:nb],
-                               stream=codec.stream)
+        state["dec"] = codec.decompress_batch(blobs, boffs[:nb], sizes, counts[:nb], out=decoded,
+                                              out_offsets=offs[:nb], stream=codec.stream)
 
     def barrier():
         sync()
@@ -547,6 +615,7 @@ def run_rank(args, rank, world, local, codec, torch, dist, device="cuda", cuda=T
                 state["ok"] &= bool((enc.status[:nb] == 0).all().item()) and bool(
                     torch.equal(decoded[: nb * S], samples[: nb * S]))
                 state["bytes"][b] = int(enc.sizes[:nb].sum().item())
+                state["last"] = (nb, enc)  # what --dump-outputs writes: the step's last batch
         if timed:
             enc_ms.append(e)
             dec_ms.append(d)
@@ -555,6 +624,9 @@ def run_rank(args, rank, world, local, codec, torch, dist, device="cuda", cuda=T
     for _ in range(args.warmup):
         step(False)
     elapsed = sum(step(True) for _ in range(args.steps))
+    if args.dump_outputs and rank == 0 and "last" in state:
+        nb, enc = state["last"]
+        dump_outputs(args.dump_outputs, args.seed, nb, S, enc, boffs, decoded, offs, state["dec"][2])
     ok = state["ok"]
     comp_rank = sum(state["bytes"])
     red_dev = device if (cuda and args.dist_backend == "nccl") else "cpu"
@@ -670,7 +742,7 @@ def main(argv=None):
 
     codec = PGNanoCodec(dev_index)
     side = {}
-    if rank == 0 and world == 1 and not args.no_side:
+    if args.full and rank == 0 and world == 1 and not args.no_side:
         side["stream_copy_gbs"] = round(stream_copy_gbs(torch), 1)
         side["pcie_inclusive"] = pcie_inclusive(torch, codec, args.samples, args.seed)
         side["per_chunk_plugin"] = per_chunk_plugin(torch, codec, args.samples, args.seed)
@@ -695,7 +767,7 @@ def main(argv=None):
                            "status_ok": bool((ev.status == 0).all().item())}
             vz.close()
             del samples
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             model, ncpu = host_info()
             line["cpu_baseline"] = cpu_baseline(S, args.cpu_sample_reads, args.seed)
             line["cpu_baseline"]["sample"] += f"; host {model}, {ncpu} logical CPUs"
@@ -703,7 +775,7 @@ def main(argv=None):
             line["cpu_baseline_all_cores"] = cpu_baseline_all_cores(S, max(8, 4 * args.cpu_sample_reads // threads),
                                                                     args.seed, threads)
             line["cpu_baseline_all_cores"]["sample"] += f"; host {model}, {ncpu} logical CPUs, CPU share {threads}"
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
     if world > 1:

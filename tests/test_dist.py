@@ -145,6 +145,53 @@ def test_bench_rank_body_strong_scaling_batches():
     assert res1[0]["compressed_bytes"] == want and "resident" in res1[0]["config"]["workload"]
 
 
+def test_bench_dump_outputs_last_step(tmp_path):
+    """--dump-outputs: sizes and statuses of every read, blobs and decoded samples of a seeded sample
+    of the reads, float32 / float64 .npy files that repeat from run to run; --steps sets the timed steps."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    import _oracle as O
+    import bench
+    from _cpu_codec import CpuCodec
+
+    reads, n = 5, 1200
+    dumps = []
+    for k, steps in enumerate((1, 2)):
+        d = tmp_path / f"run{k}"
+        args = bench.parse(["--reads", str(reads), "--samples", str(n), "--steps", str(steps), "--warmup", "0",
+                            "--dump-outputs", str(d)])
+        assert not args.full
+        codec = CpuCodec()
+        calls = []
+        encode = codec.compress_batch
+        codec.compress_batch = lambda *a, **kw: (calls.append(1), encode(*a, **kw))[1]
+        line = bench.run_rank(args, 0, 1, 0, codec, torch, dist, device="cpu", cuda=False)
+        assert line["steps"] == steps == len(calls) and line["ms_per_step"] > 0 and line["round_trip_ok"]
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["decode_status", "encode_status", "reads", "sample_blob_sizes", "sample_blobs",
+                         "sample_decoded", "sample_reads", "sizes"]
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    assert sum(v.nbytes for v in a.values()) < 64e6
+    xs = [O.synth_read(r, n) for r in range(reads)]
+    want = [O.c5_compress(x)[1] for x in xs]
+    assert a["reads"].tolist() == list(range(reads)) and a["sizes"].tolist() == [len(w) for w in want]
+    assert not a["encode_status"].any() and not a["decode_status"].any()
+    picks = a["sample_reads"].astype(int)
+    assert picks.tolist() == list(range(reads))  # a batch this small is written whole
+    assert a["sample_blobs"].astype(np.uint8).tobytes() == b"".join(want[r] for r in picks)
+    assert np.array_equal(a["sample_decoded"], np.stack([xs[r] for r in picks]).astype(np.float32))
+    # the bench's own size: a seeded sample of the reads, the same for the same arguments
+    r1, p1, L = bench.dump_picks(42, 100_000, 100_000)
+    r2, p2, _ = bench.dump_picks(42, 100_000, 100_000)
+    assert np.array_equal(p1, p2) and np.array_equal(r1, r2) and r1.size == 100_000 and L == 100_000
+    assert 1 < p1.size < 100 and np.all(np.diff(p1) > 0)
+    assert 24 * r1.size + 4 * p1.size * (3 * L + 26) < 64e6
+
+
 def test_rank_batches_partition():
     import bench
 
