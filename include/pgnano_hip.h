@@ -205,6 +205,46 @@ int pgn_variant_decompress_batch_device(pgn_ctx *ctx, int variant, size_t nchunk
                                         const uint64_t *d_sample_offsets, const uint32_t *d_sample_counts,
                                         int32_t *d_status, void *stream);
 
+/* ---- Calibrated output of the batched device decode ------------------------------------------
+ * A GPU basecaller consumes the calibrated signal pA = (adc + offset) * scale (the reference's Python
+ * reader, pod5/python/pod5/src/pod5/reader.py:356-368), not ADC counts.  This call decodes as the
+ * batch calls above do and writes that value from the merge's own stores, instead of a second pass over
+ * the decoded int16 tensor.  One entry point for every codec and both bound modes:
+ *   codec              a pgn_variant value, or PGN_POD5_CODEC_VBZ (100, pgnano_pod5.h) for VBZ
+ *   max_chunk_samples  0: no bound -- the unbounded calls above, their one host wait included (not a
+ *                      bound of 1).  Non-zero: the caller's bound on every d_sample_counts[i], as the
+ *                      _bounded calls take it; every codec is served (none gives PGN_ERR_INVALID_ARG
+ *                      for its bound), and only the staged C5 / VBZ passes space their intermediates
+ *                      for it
+ *   d_out, out_type    the output and its element type (pgn_out_type); d_out_offsets[i] is in elements
+ *                      of that type
+ *   d_cal_offset[i], d_cal_scale[i]   per chunk: the chunks of one read carry that read's calibration
+ *                      (the caller expands read -> chunk).  Required for PGN_OUT_F32 / PGN_OUT_F16,
+ *                      ignored (may be NULL) for PGN_OUT_INT16
+ * The value, exactly:
+ *   PGN_OUT_F32   s = (float)adc (exact); a = s + offset in IEEE binary32, round to nearest even;
+ *                 out = a * scale likewise.  Two roundings, no wider intermediate, no FMA -- numpy's
+ *                 (x.astype(float32) + float32(offset)) * float32(scale), bit for bit
+ *   PGN_OUT_F16   that binary32 value converted once to binary16, round to nearest even; overflow
+ *                 gives +-inf (numpy's astype(float16))
+ *   PGN_OUT_INT16 exactly what the int16 call of the codec writes
+ * Non-finite calibration values pass through the arithmetic; nothing is validated.
+ * d_status[i] is what the int16 call gives for the same blob, corrupted blobs included.  The output of
+ * a chunk whose status is not PGN_OK is unspecified, but nothing is written outside
+ * [d_out_offsets[i], + d_sample_counts[i]) of any chunk.
+ * A NULL ctx, an unknown codec or out_type, or a missing calibration array is PGN_ERR_INVALID_ARG
+ * before any GPU call.
+ * Not covered: the host-memory per-chunk calls and pgn_pod5_decompress_rows (link-bound; calibrating
+ * on the host is one line there), reading the calibration out of a POD5 reads table, normalisation,
+ * bfloat16. */
+typedef enum pgn_out_type { PGN_OUT_INT16 = 0, PGN_OUT_F32 = 1, PGN_OUT_F16 = 2 } pgn_out_type;
+
+int pgn_decompress_batch_device_pa(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nchunks,
+                                   const uint8_t *d_in, const uint64_t *d_in_offsets, const uint64_t *d_in_sizes,
+                                   void *d_out, int out_type, const uint64_t *d_out_offsets,
+                                   const uint32_t *d_sample_counts, const float *d_cal_offset,
+                                   const float *d_cal_scale, int32_t *d_status, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

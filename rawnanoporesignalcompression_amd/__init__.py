@@ -11,6 +11,7 @@ from .codec import (
     PGNanoError,
     Pod5SignalBatch,
     VBZCodec,
+    calibrate_signal,
     compress_signal,
     compressed_signal_max_size,
     decompress_signal,
@@ -29,6 +30,7 @@ __all__ = [
     "PGNanoError",
     "Pod5SignalBatch",
     "VBZCodec",
+    "calibrate_signal",
     "compress_signal",
     "compressed_signal_max_size",
     "decompress_signal",

@@ -32,6 +32,8 @@ PGN_MAX_CHUNK_SAMPLES = 16777216
 # pgn_variant: the reference's compile-time COMPRESSOR_* variants (pgnano.cpp:70-92)
 VARIANTS = {"C5": 0, "C4": 1, "C1": 2, "C2": 3, "C3": 4, "VBZ0": 5}
 PGN_STATS_PER_CHUNK = 10
+# pgn_out_type: the element type of pgn_decompress_batch_device_pa's output
+PGN_OUT_INT16, PGN_OUT_F32, PGN_OUT_F16 = 0, 1, 2
 
 # every symbol include/pgnano_hip.h declares: (name, restype, argtypes)
 _VP, _SZ, _U64P, _U32P, _I32P = C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p
@@ -66,6 +68,8 @@ SIGNATURES = [
      [_VP, C.c_int, _SZ, _VP, _U64P, _U32P, _VP, _U64P, _U64P, _U64P, _I32P, _U64P, _VP]),
     ("pgn_variant_decompress_batch_device", C.c_int,
      [_VP, C.c_int, _SZ, _VP, _U64P, _U64P, _VP, _U64P, _U32P, _I32P, _VP]),
+    ("pgn_decompress_batch_device_pa", C.c_int,
+     [_VP, C.c_int, C.c_uint32, _SZ, _VP, _U64P, _U64P, _VP, C.c_int, _U64P, _U32P, _VP, _VP, _I32P, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

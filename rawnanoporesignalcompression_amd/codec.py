@@ -18,6 +18,8 @@ Errors raise :class:`PGNanoError` carrying the reference's status message.
 
 The batched device API (:meth:`PGNanoCodec.compress_batch` / :meth:`decompress_batch`) takes
 device-resident torch tensors: one launch encodes or decodes every chunk of a batch.
+:meth:`PGNanoCodec.decompress_batch_pa` decodes straight to the calibrated signal a basecaller reads
+(float32 or float16 pA; :func:`calibrate_signal` is the same arithmetic on the host).
 """
 from __future__ import annotations
 
@@ -53,6 +55,15 @@ def _check(rc: int, detail: str = "") -> None:
 def compressed_signal_max_size(sample_count: int) -> int:
     """``pgnano::Compressor::compressed_signal_max_size`` (compressor.h:39-45)."""
     return int(_native.load().pgn_compressed_signal_max_size(sample_count))
+
+
+def calibrate_signal(adc, offset, scale, dtype=np.float32):
+    """The calibrated signal of int16 ADC counts on the host, ``pA = (adc + offset) * scale`` in float32
+    (the reference reader's ``Read.calibrate_signal_array``, pod5/python/pod5/src/pod5/reader.py:356-368):
+    the int16 converted exactly, one float32 add, one float32 multiply; ``dtype=np.float16`` rounds that
+    value once.  :meth:`PGNanoCodec.decompress_batch_pa` writes these bits from the decode kernels."""
+    pa = (np.asarray(adc, dtype=np.int16).astype(np.float32) + np.float32(offset)) * np.float32(scale)
+    return pa if np.dtype(dtype) == np.float32 else pa.astype(dtype)
 
 
 def _ptr(t) -> int:
@@ -255,6 +266,77 @@ class PGNanoCodec:
         caller.wait_stream(ls)
         return out, so, status
 
+    @property
+    def _pa_codec(self) -> int:
+        """This codec's id for pgn_decompress_batch_device_pa (a pgn_variant value)."""
+        return _native.VARIANTS[self.variant]
+
+    def decompress_batch_pa(self, blobs, blob_offsets, blob_sizes, sample_counts, cal_offset, cal_scale,
+                            dtype=None, out=None, out_offsets=None, stream: int | None = None,
+                            max_chunk_samples: int | None = None):
+        """Decode a device-resident batch straight to the calibrated signal; returns (out, offsets, status).
+
+        The merge kernels write ``pA = (adc + offset) * scale`` themselves (pgn_decompress_batch_device_pa),
+        so no second pass reads the int16 samples back.  dtype: ``torch.float32`` (default; exactly
+        ``(adc.astype(float32) + float32(offset)) * float32(scale)``, the reference reader's
+        ``calibrate_signal_array``), ``torch.float16`` (that value rounded once, to nearest even), or
+        ``torch.int16`` (the samples :meth:`decompress_batch` writes).
+
+        cal_offset, cal_scale: float32 tensors with one entry per chunk (ignored for int16, may be
+        None).  Calibration belongs to a read, and the chunks of a read share it, so expand the reads'
+        values with the chunks' read indices::
+
+            cal_offset = cal_offset_read[read_index]    # read_index[i]: the read chunk i belongs to
+            cal_scale = cal_scale_read[read_index]
+
+        out / out_offsets: the destination (of ``dtype``, on the device) and the chunks' places in it,
+        in elements.  stream and max_chunk_samples as in :meth:`decompress_batch`; here the bound is
+        accepted for every codec and must be > 0 when given."""
+        import torch
+
+        dtype = torch.float32 if dtype is None else dtype
+        types = {torch.int16: _native.PGN_OUT_INT16, torch.float32: _native.PGN_OUT_F32,
+                 torch.float16: _native.PGN_OUT_F16}
+        if dtype not in types:
+            raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.int16 (got {dtype})")
+        if max_chunk_samples is not None and int(max_chunk_samples) <= 0:
+            raise ValueError("max_chunk_samples must be > 0 when given (None: no bound)")
+        _require_device(blobs, "blobs", self.device)
+        n = int(sample_counts.numel())
+        if out is not None:
+            _require_device(out, "out", self.device)
+            if out.dtype != dtype:
+                raise ValueError(f"out must have dtype {dtype} (got {out.dtype})")
+        calibrated = dtype != torch.int16
+        if calibrated:
+            for t, name in ((cal_offset, "cal_offset"), (cal_scale, "cal_scale")):
+                if t is None or int(t.numel()) != n:
+                    raise ValueError(f"{name} must have one entry per chunk ({n})")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = blobs.device
+            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
+            if out_offsets is None:
+                so = torch.zeros(n, dtype=torch.int64, device=dev)
+                if n > 1:
+                    so[1:] = torch.cumsum(counts.to(torch.int64), 0)[:-1]
+            else:
+                so = out_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            if out is None:
+                total = int(counts.to(torch.int64).sum().item())
+                out = torch.empty(max(total, 1), dtype=dtype, device=dev)
+            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
+            co = cal_offset.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
+            cs = cal_scale.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
+            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            _check(self._lib.pgn_decompress_batch_device_pa(
+                self._h, self._pa_codec, int(max_chunk_samples or 0), n, _ptr(blobs), _ptr(bo), _ptr(bs), _ptr(out),
+                types[dtype], _ptr(so), _ptr(counts), _ptr(co), _ptr(cs), _ptr(status), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return out, so, status
+
     def synth_reads(self, nreads: int, samples_per_read, seed: int = 42, first_read: int = 0, read_stride: int = 1,
                     p_switch_q16: int = 6554, level_mean: int = 500, level_sd: int = 60, noise_sd: int = 12,
                     out=None):
@@ -302,6 +384,10 @@ class VBZCodec(PGNanoCodec):
 
     def __init__(self, device: int = 0):
         super().__init__(device)
+
+    @property
+    def _pa_codec(self) -> int:
+        return _native.PGN_POD5_CODEC_VBZ
 
     @staticmethod
     def max_size(sample_count: int) -> int:

@@ -502,6 +502,111 @@ __device__ __forceinline__ void put_bytes16(uint16_t* d, const uint4& v, uint32_
     q[1] = make_uint4(o[4], o[5], o[6], o[7]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The sample sink: where every merge's samples leave.  A lane holds the 16 consecutive samples
+// t + 16 lane .. + 15 of a step as two 16-bit values per dword (w[8]); T is the output element:
+//   int16_t   the ADC counts, two 16-byte stores per lane;
+//   float     the calibrated signal pA = (adc + offset) * scale -- the int16 converted exactly, one
+//             binary32 add, one binary32 multiply (two roundings; an add feeding a multiply cannot
+//             contract to an FMA), the arithmetic of the reference's reader (pod5/python/pod5/src/
+//             pod5/reader.py:356-368) -- four samples converted and stored at a time, four 16-byte
+//             stores per lane (a wave writes 4 KiB contiguous);
+//   _Float16  that binary32 value converted once to binary16, round to nearest even (overflow to
+//             +-inf), pairs packed: two 16-byte stores per lane, the bytes the int16 output writes.
+// cal is the chunk's calibration, wave-uniform (unused for int16_t).  NT: full steps of the 2-byte
+// outputs leave as non-temporal stores when the lane's destination address is 16-byte aligned
+// (merge_step; the other merges store plainly); float stores are always plain (see below).  A ragged step (!full) stores per sample and touches nothing at or past n.
+// ---------------------------------------------------------------------------------------------
+struct Cal {
+    float off, scale;
+};
+__device__ __forceinline__ float cal_pa(int32_t adc, Cal cal) { return ((float)adc + cal.off) * cal.scale; }
+// the two samples of a dword -> pA
+__device__ __forceinline__ float cal_lo(uint32_t w, Cal cal) { return cal_pa((int32_t)(int16_t)(uint16_t)w, cal); }
+__device__ __forceinline__ float cal_hi(uint32_t w, Cal cal) { return cal_pa((int32_t)w >> 16, cal); }
+// binary32 -> binary16 bits, round to nearest even.  The value passes through an empty asm first: the
+// conversion must see the rounded binary32 product.  Left visible, the compiler fuses the multiply
+// and the conversion into v_fma_mixlo_f16, which rounds the exact product once -- a different
+// binary16 wherever the binary32 value is a tie (measured: 7 of 25.6 M bench samples).
+__device__ __forceinline__ uint32_t f16_bits(float f)
+{
+    asm("" : "+v"(f));
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+}
+
+template <class T>
+constexpr bool kIsAdc = false;
+template <>
+constexpr bool kIsAdc<int16_t> = true;
+
+template <bool NT, class T>
+__device__ __forceinline__ void sink_samples16(T* __restrict__ out, const uint32_t (&w)[8], uint32_t t, uint32_t n, bool full,
+                                               Cal cal)
+{
+    const uint32_t lane = (uint32_t)lane_id();
+    T* dst = out + t + 16u * lane;
+    if constexpr (kIsAdc<T> && NT) {
+        if (full) {
+            // the samples are written once: non-temporal stores (they do not displace the streams the
+            // other decode kernels are reading from L2; bench-size decode 22.3-22.6 -> 21.8-21.9 ms)
+            if (((uintptr_t)dst & 15u) == 0) {
+                gst_nt16(dst, make_uint4(w[0], w[1], w[2], w[3]));
+                gst_nt16(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
+            } else {
+                gst<uint4>(dst, make_uint4(w[0], w[1], w[2], w[3]));
+                gst<uint4>(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
+            }
+        } else {
+            for (uint32_t m = 0; m < 16 && t + 16u * lane + m < n; m++) gst<uint16_t>(dst + m, (uint16_t)(w[m >> 1] >> (16 * (m & 1))));
+        }
+    } else if constexpr (kIsAdc<T>) {
+        if (full) {
+            gst<uint4>(dst, make_uint4(w[0], w[1], w[2], w[3]));
+            gst<uint4>(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
+        } else {
+#pragma unroll
+            for (int m = 0; m < 16; m++)
+                if (t + 16u * lane + (uint32_t)m < n) gst<uint16_t>(dst + m, (uint16_t)(w[m >> 1] >> (16 * (m & 1))));
+        }
+    } else if constexpr (sizeof(T) == 4) {
+        if (full) {
+            // Plain stores, aligned or not: each of a lane's four stores covers a quarter of its 64
+            // bytes, and as non-temporal stores those quarters reach memory separately (bench-size C5
+            // decode to float32: 75.5 ms non-temporal, 34.7 ms plain, profiles/decode_pa_timing.log);
+            // written back from L2 the lines leave whole.
+#pragma unroll
+            for (int q = 0; q < 4; q++) {  // four samples at a time: 16 floats are never held together
+                const uint4 v = make_uint4(__float_as_uint(cal_lo(w[2 * q], cal)), __float_as_uint(cal_hi(w[2 * q], cal)),
+                                           __float_as_uint(cal_lo(w[2 * q + 1], cal)), __float_as_uint(cal_hi(w[2 * q + 1], cal)));
+                gst<uint4>(dst + 4 * q, v);
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < 16; m++)
+                if (t + 16u * lane + (uint32_t)m < n)
+                    gst<uint32_t>(dst + m, __float_as_uint((m & 1) ? cal_hi(w[m >> 1], cal) : cal_lo(w[m >> 1], cal)));
+        }
+    } else {
+        if (full) {
+            uint32_t h[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) h[k] = f16_bits(cal_lo(w[k], cal)) | (f16_bits(cal_hi(w[k], cal)) << 16);
+            if (NT && ((uintptr_t)dst & 15u) == 0) {
+                gst_nt16(dst, make_uint4(h[0], h[1], h[2], h[3]));
+                gst_nt16(dst + 8, make_uint4(h[4], h[5], h[6], h[7]));
+            } else {
+                gst<uint4>(dst, make_uint4(h[0], h[1], h[2], h[3]));
+                gst<uint4>(dst + 8, make_uint4(h[4], h[5], h[6], h[7]));
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < 16; m++)
+                if (t + 16u * lane + (uint32_t)m < n)
+                    gst<uint16_t>(dst + m, (uint16_t)f16_bits((m & 1) ? cal_hi(w[m >> 1], cal) : cal_lo(w[m >> 1], cal)));
+        }
+    }
+}
+
 // Merge step over 1024 samples: lane l decodes the 16 consecutive samples t + 16l .. t + 16l + 15,
 // whose 16 keys are its own key word.  Every class has a staged 16-bit window of deltas (offsets
 // added and zig-zag decoded at staging; class 0 reads zeros), and the lane's first place in each is
@@ -510,11 +615,11 @@ __device__ __forceinline__ void put_bytes16(uint16_t* d, const uint4& v, uint32_
 // is field c_m (one v_perm_b32 whose selector is c_m * 0x0202 + 0x0C0C0100), and the field advances
 // by one entry (2 << 16 c_m, a 64-bit shift and add).  So a sample is four ALU ops to its place, one
 // LDS read and a running 16-bit sum, and a second scan carries the sum across lanes.  Outputs leave
-// as two 16-byte stores per lane.
+// through the sample sink (int16_t: two 16-byte stores per lane).
+template <class T>
 __device__ __forceinline__ void merge_step(const MergeLds& W, uint32_t kw, uint32_t pS, uint32_t pM, uint32_t pL,
-                                           uint32_t& carry, int16_t* __restrict__ out, uint32_t t, uint32_t n, bool full)
+                                           uint32_t& carry, T* __restrict__ out, uint32_t t, uint32_t n, bool full, Cal cal)
 {
-    const uint32_t lane = (uint32_t)lane_id();
     const uint8_t* wb = reinterpret_cast<const uint8_t*>(&W);
     constexpr uint32_t pZ = (uint32_t)__builtin_offsetof(MergeLds, zero);
     // places are below sizeof(MergeLds) < 2^16
@@ -547,20 +652,7 @@ __device__ __forceinline__ void merge_step(const MergeLds& W, uint32_t kw, uint3
     const pgn_u16x2 base2 = as_u16x2((base & 0xFFFFu) * 0x00010001u);
 #pragma unroll
     for (int k = 0; k < 8; k++) w[k] = as_u32(as_u16x2(w[k]) + base2);
-    int16_t* dst = out + t + 16u * lane;
-    if (full) {
-        // the samples are written once: non-temporal stores (they do not displace the streams the
-        // other decode kernels are reading from L2; bench-size decode 22.3-22.6 -> 21.8-21.9 ms)
-        if (((uintptr_t)dst & 15u) == 0) {
-            gst_nt16(dst, make_uint4(w[0], w[1], w[2], w[3]));
-            gst_nt16(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
-        } else {
-            gst<uint4>(dst, make_uint4(w[0], w[1], w[2], w[3]));
-            gst<uint4>(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
-        }
-    } else {
-        for (uint32_t m = 0; m < 16 && t + 16u * lane + m < n; m++) gst<uint16_t>(dst + m, (uint16_t)(w[m >> 1] >> (16 * (m & 1))));
-    }
+    sink_samples16<true>(out, w, t, n, full, cal);
 }
 
 // One step's bookkeeping, computed two steps ahead: the key word, the class counts below this lane,
@@ -592,11 +684,11 @@ struct MergeBytes {
 #endif
 constexpr uint32_t kMergeAhead = PGN_MERGE_AHEAD;
 static_assert(kMergeAhead == 1 || kMergeAhead == 2, "merge lookahead");
-template <bool C4 = false>
+template <bool C4 = false, class T = int16_t>
 __device__ __forceinline__ int c5_merge_range(const uint8_t* __restrict__ in, uint64_t total, uint64_t dS, uint64_t dM,
-                                              uint64_t dLl, int16_t* __restrict__ out, uint32_t n, uint32_t t0,
+                                              uint64_t dLl, T* __restrict__ out, uint32_t n, uint32_t t0,
                                               uint32_t t1, uint64_t sN0, uint64_t mN0, uint64_t lN0, uint32_t& carry,
-                                              uint64_t* lEnd, MergeLds& W)
+                                              uint64_t* lEnd, MergeLds& W, Cal cal = Cal{0.f, 0.f})
 {
     using CO = ClassOffsets<C4>;
     const uint32_t lane = (uint32_t)lane_id();
@@ -728,7 +820,7 @@ __device__ __forceinline__ int c5_merge_range(const uint8_t* __restrict__ in, ui
         }
         kwN1 = kwN2;
         if (j + D + 2 < nsteps) kwN2 = key_word(tof(j + D + 2));
-        merge_step(W, kw, pS, pM, pL, carry, out, t, n, full);
+        merge_step(W, kw, pS, pM, pL, carry, out, t, n, full, cal);
         lds_sync();
         return true;
     };
@@ -746,15 +838,15 @@ __device__ __forceinline__ int c5_merge_range(const uint8_t* __restrict__ in, ui
     return 0;
 }
 
-template <bool C4 = false>
+template <bool C4 = false, class T = int16_t>
 __device__ __forceinline__ int c5_merge_wave(const uint8_t* __restrict__ in, uint64_t total, uint64_t dS, uint64_t dM,
-                                             uint64_t dLl, int16_t* __restrict__ out, uint32_t n, uint64_t* consumed,
-                                             MergeLds& W)
+                                             uint64_t dLl, T* __restrict__ out, uint32_t n, uint64_t* consumed,
+                                             MergeLds& W, Cal cal = Cal{0.f, 0.f})
 {
     const uint64_t kl = ((uint64_t)n + 3) / 4;
     uint32_t carry = 0;
     uint64_t lN = 0;
-    const int bad = c5_merge_range<C4>(in, total, dS, dM, dLl, out, n, 0u, n, 0, 0, 0, carry, &lN, W);
+    const int bad = c5_merge_range<C4>(in, total, dS, dM, dLl, out, n, 0u, n, 0, 0, 0, carry, &lN, W, cal);
     if (bad) return bad;
     *consumed = kl + dS + dM + dLl + lN;
     return 0;
@@ -764,7 +856,7 @@ __device__ __forceinline__ int c5_merge_wave(const uint8_t* __restrict__ in, uin
 // reduction over the range's stretches of the S / M / class-3 streams: S nibbles [s0, s1) at ps
 // (low nibble first), M bytes [m0, m1) at pm, class-3 pairs [l0, l1) at pl / ph.  Wave-uniform.
 template <bool C4 = false>
-__device__ inline uint32_t c5_range_delta_sum(const uint8_t* __restrict__ in, uint64_t ps, uint64_t pm, uint64_t pl,
+__device__ __forceinline__ uint32_t c5_range_delta_sum(const uint8_t* __restrict__ in, uint64_t ps, uint64_t pm, uint64_t pl,
                                               uint64_t ph, uint64_t s0, uint64_t s1, uint64_t m0, uint64_t m1,
                                               uint64_t l0, uint64_t l1)
 {

@@ -507,7 +507,28 @@ struct DecArgs {
     uint8_t* jobs;       // [G][5] HufJob records (pgn_hufjob.h): dec_zstd_kernel defers, dec_huf_kernel decodes; null = in place
     uint32_t hufPrio;    // dec_huf_kernel waves at raised priority (the last deferred pass: the decode's drain)
     uint64_t interBytes; // dec_chunk_kernel's claims pass: the slot intermediate's bytes (0: inter_cap(capN))
+    // calibrated output (pgn_decompress_batch_device_pa): the output as bytes, its element type
+    // (pgn_out_type; sampleOffsets are in elements of it) and the per-chunk calibration.
+    // PGN_OUT_INT16 (0): the kernels write `samples`
+    uint8_t* outBytes;
+    int32_t outType;
+    const float* calOffset;
+    const float* calScale;
 };
+
+// chunk c's destination and calibration for the output element T (wave-uniform)
+template <class T>
+__device__ __forceinline__ T* out_chunk(const DecArgs& a, size_t c)
+{
+    if constexpr (kIsAdc<T>) return a.samples + a.sampleOffsets[c];
+    else return reinterpret_cast<T*>(a.outBytes) + a.sampleOffsets[c];
+}
+template <class T>
+__device__ __forceinline__ Cal cal_chunk(const DecArgs& a, size_t c)
+{
+    if constexpr (kIsAdc<T>) return Cal{0.f, 0.f};
+    else return Cal{uni(a.calOffset[c]), uni(a.calScale[c])};
+}
 
 // The status of a chunk whose frames claim more content (ZSTD_getFrameContentSize) than the
 // decoder's intermediate holds.  The reference allocates the sum of the claims (a size_t sum,
@@ -1171,13 +1192,15 @@ __global__ __launch_bounds__(64 * kCoopWaves) void dec_zstd_coop_kernel(DecArgs 
     P.flush();
 }
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void dec_merge_kernel(DecArgs a)
+// The staged C5 merge, one wave per chunk, for the output element T (the sample sink, pgn_c5.h):
+// dec_merge_kernel writes the int16 samples, dec_merge_pa_kernel<float / _Float16> the calibrated ones.
+template <class T>
+__device__ __forceinline__ void dec_merge_body(const DecArgs& a, MergeLds& W)
 {
     const size_t g = blockIdx.x;
     const size_t c = a.base + g;
     if (g >= a.G || c >= a.nchunks) return;
     if (a.status[c] != PGN_OK) return;
-    static __shared__ MergeLds W;
     PhaseProf P;
     P.init(a.prof);
 #if PGN_MERGE_DIAG == 1  // diagnostic: chunk g merges chunk g % 32's intermediate (L2-resident reads, same work on equal-size chunks)
@@ -1195,13 +1218,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void de
     if (st == PGN_OK) {
         uint64_t consumed = 0;
         const int bad = c5_merge_wave(a.inter + gi * a.interStride, total, (uint64_t)d[1].dres, (uint64_t)d[2].dres,
-                                      (uint64_t)d[3].dres, a.samples + a.sampleOffsets[c], a.sampleCounts[c], &consumed, W);
+                                      (uint64_t)d[3].dres, out_chunk<T>(a, c), a.sampleCounts[c], &consumed, W,
+                                      cal_chunk<T>(a, c));
         if (bad) st = PGN_ERR_CORRUPT;
         else if (consumed != total) st = PGN_ERR_REMAINING;
     }
     if (lane_id() == 0) a.status[c] = st;
     P.mark(6);
     P.flush();
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void dec_merge_kernel(DecArgs a)
+{
+    static __shared__ MergeLds W;
+    dec_merge_body<int16_t>(a, W);
+}
+template <class T>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void dec_merge_pa_kernel(DecArgs a)
+{
+    static __shared__ MergeLds W;
+    dec_merge_body<T>(a, W);
 }
 
 constexpr size_t kMergeWgMaxChunks = 64;  // batches up to this many chunks take the small-batch kernels
@@ -1214,7 +1250,8 @@ constexpr size_t kMergeWgMaxChunks = 64;  // batches up to this many chunks take
 // only waits on lower-numbered ones, which the dispatcher started first.  The last range sets the
 // status once every range is done.  Same bytes and statuses as dec_merge_kernel.
 constexpr int kMergeRanges = 32;
-__global__ __launch_bounds__(64) void dec_merge_lb_kernel(DecArgs a)
+template <class T>
+__device__ __forceinline__ void dec_merge_lb_body(const DecArgs& a, MergeLds& W)
 {
     const size_t g = blockIdx.x / kMergeRanges;
     const uint32_t r = blockIdx.x % kMergeRanges;
@@ -1238,12 +1275,11 @@ __global__ __launch_bounds__(64) void dec_merge_lb_kernel(DecArgs a)
         if (r == 0 && lane == 0) a.status[c] = st;
         return;
     }
-    __shared__ MergeLds W;
     uint64_t* lb = a.lookback + g * (3 * kMergeRanges);
     const uint64_t ep = a.epoch;
     const uint32_t n = a.sampleCounts[c];
     const uint8_t* in = a.inter + g * a.interStride;
-    int16_t* out = a.samples + a.sampleOffsets[c];
+    T* out = out_chunk<T>(a, c);
     const uint64_t dS = (uint64_t)d[1].dres, dM = (uint64_t)d[2].dres, dLl = (uint64_t)d[3].dres;
     const uint64_t kl = ((uint64_t)n + 3) / 4;
     const uint64_t ps = kl, pm = kl + dS, pl = kl + dS + dM, ph = kl + dS + dM + dLl;
@@ -1271,7 +1307,7 @@ __global__ __launch_bounds__(64) void dec_merge_lb_kernel(DecArgs a)
     if (!bad) {
         uint32_t carry = carryIn;
         uint64_t lEnd = 0;
-        bad = c5_merge_range<false>(in, total, dS, dM, dLl, out, n, t0, t1, sN0, mN0, lN0, carry, &lEnd, W);
+        bad = c5_merge_range<false>(in, total, dS, dM, dLl, out, n, t0, t1, sN0, mN0, lN0, carry, &lEnd, W, cal_chunk<T>(a, c));
     }
     if (lane == 0) lb_publish(lb + 3 * r + 2, ep, (uint64_t)(bad ? 1u : 0u));
     // 4. the last range: every range done -> status
@@ -1285,6 +1321,19 @@ __global__ __launch_bounds__(64) void dec_merge_lb_kernel(DecArgs a)
         }
     }
 }
+
+__global__ __launch_bounds__(64) void dec_merge_lb_kernel(DecArgs a)
+{
+    __shared__ MergeLds W;
+    dec_merge_lb_body<int16_t>(a, W);
+}
+template <class T>
+__global__ __launch_bounds__(64) void dec_merge_lb_pa_kernel(DecArgs a)
+{
+    __shared__ MergeLds W;
+    dec_merge_lb_body<T>(a, W);
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // VBZ (pod5::compress_signal / decompress_signal, signal_compression.cpp:37-141): split -> one
@@ -1372,13 +1421,13 @@ __global__ __launch_bounds__(64) void vbz_parse_kernel(DecArgs a)
     a.status[c] = st;
 }
 
-__global__ __launch_bounds__(64) void vbz_merge_kernel(DecArgs a)
+template <class T>
+__device__ __forceinline__ void vbz_merge_body(const DecArgs& a, VbzMergeLds& W)
 {
     const size_t g = blockIdx.x;
     const size_t c = a.base + g;
     if (g >= a.G || c >= a.nchunks) return;
     if (a.status[c] != PGN_OK) return;
-    static __shared__ VbzMergeLds W;
     PhaseProf P;
     P.init(a.prof);
     const DecUnit* d = a.units + g * kStreams;
@@ -1395,8 +1444,8 @@ __global__ __launch_bounds__(64) void vbz_merge_kernel(DecArgs a)
         if (svb_key_length(n) > d->cs) {  // keys alone run into the padding (or past it)
             st = svb_key_length(n) <= total ? PGN_ERR_REMAINING : PGN_ERR_CORRUPT;
         } else {
-            const int bad = vbz_merge_wave(a.inter + g * a.interStride, total, a.samples + a.sampleOffsets[c], n,
-                                           &consumed, W);
+            const int bad = vbz_merge_wave(a.inter + g * a.interStride, total, out_chunk<T>(a, c), n, &consumed, W,
+                                           cal_chunk<T>(a, c));
             if (bad) st = PGN_ERR_CORRUPT;
             else if (consumed != d->cs) st = PGN_ERR_REMAINING;
         }
@@ -1404,6 +1453,18 @@ __global__ __launch_bounds__(64) void vbz_merge_kernel(DecArgs a)
     if (lane_id() == 0) a.status[c] = st;
     P.mark(6);
     P.flush();
+}
+
+__global__ __launch_bounds__(64) void vbz_merge_kernel(DecArgs a)
+{
+    static __shared__ VbzMergeLds W;
+    vbz_merge_body<int16_t>(a, W);
+}
+template <class T>
+__global__ __launch_bounds__(64) void vbz_merge_pa_kernel(DecArgs a)
+{
+    static __shared__ VbzMergeLds W;
+    vbz_merge_body<T>(a, W);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1484,33 +1545,48 @@ struct MergeOut {
     int bad;
     uint64_t consumed;
 };
-template <bool C4>
+// T: the output element of the sample sink; its calibration arrives with the other arguments (none
+// for the int16 samples: an empty argument)
+template <class T>
+struct CalArg {
+    float off, scale;
+    __device__ __forceinline__ Cal get() const { return Cal{uni(off), uni(scale)}; }
+};
+template <>
+struct CalArg<int16_t> {
+    __device__ __forceinline__ Cal get() const { return Cal{0.f, 0.f}; }
+};
+template <bool C4, class T>
 __device__ __noinline__ MergeOut c5_merge_chunk(const uint8_t* in, uint64_t total, uint64_t dS, uint64_t dM, uint64_t dLl,
-                                                int16_t* out, uint32_t n)
+                                                T* out, uint32_t n, CalArg<T> ca)
 {
     MergeOut o{0, 0};
     o.bad = c5_merge_wave<C4>(uni(in), uni(total), uni(dS), uni(dM), uni(dLl), uni(out), uni(n), &o.consumed,
-                              *reinterpret_cast<MergeLds*>(&sDec));
+                              *reinterpret_cast<MergeLds*>(&sDec), ca.get());
     return o;
 }
-template <bool C3>
-__device__ __noinline__ MergeOut c23_merge_chunk(const uint8_t* in, uint64_t total, uint64_t dA, uint64_t dB, int16_t* out,
-                                                 uint32_t n)
+template <bool C3, class T>
+__device__ __noinline__ MergeOut c23_merge_chunk(const uint8_t* in, uint64_t total, uint64_t dA, uint64_t dB, T* out,
+                                                 uint32_t n, CalArg<T> ca)
 {
     MergeOut o{0, 0};
-    o.bad = c23_merge_wave<C3>(uni(in), uni(total), uni(dA), uni(dB), uni(out), uni(n), &o.consumed);
+    o.bad = c23_merge_wave<C3>(uni(in), uni(total), uni(dA), uni(dB), uni(out), uni(n), &o.consumed, ca.get());
     return o;
 }
-__device__ __noinline__ MergeOut vbz_merge_chunk(const uint8_t* in, uint64_t total, int16_t* out, uint32_t n)
+template <class T>
+__device__ __noinline__ MergeOut vbz_merge_chunk(const uint8_t* in, uint64_t total, T* out, uint32_t n, CalArg<T> ca)
 {
     MergeOut o{0, 0};
-    o.bad = vbz_merge_wave(uni(in), uni(total), uni(out), uni(n), &o.consumed, *reinterpret_cast<VbzMergeLds*>(&sDec));
+    o.bad = vbz_merge_wave(uni(in), uni(total), uni(out), uni(n), &o.consumed, *reinterpret_cast<VbzMergeLds*>(&sDec),
+                           ca.get());
     return o;
 }
-__device__ __noinline__ MergeOut vbz0_merge_chunk(const uint8_t* in, uint64_t total, int16_t* out, uint32_t n)
+template <class T>
+__device__ __noinline__ MergeOut vbz0_merge_chunk(const uint8_t* in, uint64_t total, T* out, uint32_t n, CalArg<T> ca)
 {
     MergeOut o{0, 0};
-    o.bad = vbz0_merge_wave(uni(in), uni(total), uni(out), uni(n), &o.consumed, *reinterpret_cast<Vbz0MergeLds*>(&sDec));
+    o.bad = vbz0_merge_wave(uni(in), uni(total), uni(out), uni(n), &o.consumed, *reinterpret_cast<Vbz0MergeLds*>(&sDec),
+                            ca.get());
     return o;
 }
 
@@ -1691,6 +1767,35 @@ __device__ inline int parse_frames(const uint8_t* in, uint64_t src0, uint64_t le
     return PGN_OK;
 }
 
+// the merge of one chunk's decoded frames (d, in the intermediate `inter`) by codec
+template <int Codec, class T>
+__device__ __forceinline__ MergeOut merge_chunk(const uint8_t* inter, uint64_t total, const DecUnit* d, T* out, uint32_t n,
+                                                CalArg<T> ca)
+{
+    MergeOut mo{0, 0};
+    if (Codec == kCodecVbz) {
+        // svb16::decode over content + 16 padding bytes, then "consumed + padding == size"
+        // (signal_compression.cpp:100-131): keys running into the padding are "Remaining data"
+        const uint64_t padded = total + kVbzPadding;
+        if (svb_key_length(n) > total) {
+            mo.bad = svb_key_length(n) <= padded ? 2 : 1;
+        } else {
+            mo = vbz_merge_chunk(inter, padded, out, n, ca);
+        }
+    } else if (Codec == kCodecC1) {
+        mo = vbz_merge_chunk(inter, total, out, n, ca);
+    } else if (Codec == kCodecVbz0) {
+        mo = vbz0_merge_chunk(inter, total, out, n, ca);
+    } else if (Codec == kCodecC2 || Codec == kCodecC3) {
+        mo = c23_merge_chunk<Codec == kCodecC3>(inter, total, (uint64_t)d[1].dres,
+                                                Codec == kCodecC3 ? (uint64_t)d[2].dres : 0ull, out, n, ca);
+    } else {
+        mo = c5_merge_chunk<Codec == kCodecC4>(inter, total, (uint64_t)d[1].dres, (uint64_t)d[2].dres,
+                                               (uint64_t)d[3].dres, out, n, ca);
+    }
+    return mo;
+}
+
 template <int Codec>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void dec_chunk_kernel(DecArgs a)
 {
@@ -1718,7 +1823,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void de
         if (u >= a.nchunks) break;
         const size_t c = a.list ? a.list[u] : u;
         const uint32_t n = a.sampleCounts[c];
-        int16_t* out = a.samples + a.sampleOffsets[c];
         DecUnit d[kStreams];
         uint64_t total = 0;
         // the claims pass (a.interBytes): any sample count, the frames in an intermediate sized from
@@ -1756,26 +1860,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void de
         if (st == PGN_OK) {
             MergeOut mo{0, 0};
             uint64_t want = total;  // the pgnano svb16 decoders need no padding: consume everything
-            if (Codec == kCodecVbz) {
-                // svb16::decode over content + 16 padding bytes, then "consumed + padding == size"
-                // (signal_compression.cpp:100-131): keys running into the padding are "Remaining data"
-                const uint64_t padded = total + kVbzPadding;
-                if (svb_key_length(n) > total) {
-                    mo.bad = svb_key_length(n) <= padded ? 2 : 1;
-                } else {
-                    mo = vbz_merge_chunk(inter, padded, out, n);
-                }
-            } else if (Codec == kCodecC1) {
-                mo = vbz_merge_chunk(inter, total, out, n);
-            } else if (Codec == kCodecVbz0) {
-                mo = vbz0_merge_chunk(inter, total, out, n);
-            } else if (Codec == kCodecC2 || Codec == kCodecC3) {
-                mo = c23_merge_chunk<Codec == kCodecC3>(inter, total, (uint64_t)d[1].dres,
-                                                        Codec == kCodecC3 ? (uint64_t)d[2].dres : 0ull, out, n);
-            } else {
-                mo = c5_merge_chunk<Codec == kCodecC4>(inter, total, (uint64_t)d[1].dres, (uint64_t)d[2].dres,
-                                                       (uint64_t)d[3].dres, out, n);
-            }
+            // the merge for the call's output element: a wave-uniform branch between non-inlined calls
+            if (a.outType == PGN_OUT_F32)
+                mo = merge_chunk<Codec>(inter, total, d, out_chunk<float>(a, c), n, CalArg<float>{a.calOffset[c], a.calScale[c]});
+            else if (a.outType == PGN_OUT_F16)
+                mo = merge_chunk<Codec>(inter, total, d, out_chunk<_Float16>(a, c), n,
+                                        CalArg<_Float16>{a.calOffset[c], a.calScale[c]});
+            else mo = merge_chunk<Codec>(inter, total, d, out_chunk<int16_t>(a, c), n, CalArg<int16_t>{});
             if (mo.bad == 2) st = PGN_ERR_REMAINING;
             else if (mo.bad) st = PGN_ERR_CORRUPT;
             else if (mo.consumed != want) st = PGN_ERR_REMAINING;
@@ -2326,6 +2417,24 @@ static int ensure_queues(pgn_ctx* c, size_t n, hipStream_t s)
     return PGN_OK;
 }
 
+// A decode call's destination: the int16 samples (what an int16_t* converts to), or the calibrated
+// output of pgn_decompress_batch_device_pa (element type and per-chunk calibration).
+struct DecOut {
+    void* p;
+    int type;
+    const float *calOffset, *calScale;
+    DecOut(int16_t* samples) : p(samples), type(PGN_OUT_INT16), calOffset(nullptr), calScale(nullptr) {}
+    DecOut(void* out, int t, const float* off, const float* scale) : p(out), type(t), calOffset(off), calScale(scale) {}
+};
+static void set_out(DecArgs& a, const DecOut& o)
+{
+    a.samples = (int16_t*)o.p;
+    a.outBytes = (uint8_t*)o.p;
+    a.outType = o.type;
+    a.calOffset = o.calOffset;
+    a.calScale = o.calScale;
+}
+
 static int launch_enc_chunks(int codec, const EncArgs& a, size_t slots, hipStream_t s);
 static int launch_dec_chunks(int codec, const DecArgs& a, size_t slots, hipStream_t s);
 
@@ -2378,7 +2487,7 @@ static int launch_enc_chunks(int codec, const EncArgs& a, size_t slots, hipStrea
 }
 
 static int launch_decode_fused(pgn_ctx* c, int codec, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                               const uint64_t* d_in_sizes, int16_t* d_samples, const uint64_t* d_sample_offsets,
+                               const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
                                const uint32_t* d_sample_counts, int32_t* d_status, hipStream_t s)
 {
     const size_t slots = nchunks < c->decFusedSlotsMax ? nchunks : c->decFusedSlotsMax;
@@ -2392,7 +2501,7 @@ static int launch_decode_fused(pgn_ctx* c, int codec, size_t nchunks, const uint
     a.in = d_in;
     a.inOffsets = d_in_offsets;
     a.inSizes = d_in_sizes;
-    a.samples = d_samples;
+    set_out(a, d_samples);
     a.sampleOffsets = d_sample_offsets;
     a.sampleCounts = d_sample_counts;
     a.status = d_status;
@@ -2509,10 +2618,28 @@ static int launch_encode_impl(pgn_ctx* c, int codec, size_t nchunks, const int16
     return PGN_OK;
 }
 
+// The staged passes' merge for the call's output element (a.outType).
+#define PGN_LAUNCH_MERGE_PA(T)                                                                                           \
+    do {                                                                                                                 \
+        if (codec == kCodecVbz) hipLaunchKernelGGL(vbz_merge_pa_kernel<T>, dim3((unsigned)G), dim3(64), 0, ms, a);       \
+        else if (a.lookback)                                                                                             \
+            hipLaunchKernelGGL(dec_merge_lb_pa_kernel<T>, dim3((unsigned)(G * kMergeRanges)), dim3(64), 0, ms, a);       \
+        else hipLaunchKernelGGL(dec_merge_pa_kernel<T>, dim3((unsigned)G), dim3(64), 0, ms, a);                          \
+    } while (0)
+static void launch_merge(int codec, const DecArgs& a, size_t G, hipStream_t ms)
+{
+    if (a.outType == PGN_OUT_F32) PGN_LAUNCH_MERGE_PA(float);
+    else if (a.outType == PGN_OUT_F16) PGN_LAUNCH_MERGE_PA(_Float16);
+    else if (codec == kCodecVbz) hipLaunchKernelGGL(vbz_merge_kernel, dim3((unsigned)G), dim3(64), 0, ms, a);
+    else if (a.lookback)  // few chunks: kMergeRanges single-wave workgroups per chunk
+        hipLaunchKernelGGL(dec_merge_lb_kernel, dim3((unsigned)(G * kMergeRanges)), dim3(64), 0, ms, a);
+    else hipLaunchKernelGGL(dec_merge_kernel, dim3((unsigned)G), dim3(64), 0, ms, a);
+}
+
 // capCall: every chunk of the call has at most this many samples (a multiple of 4096, at most
 // kPassSamples); the per-chunk intermediates are spaced for it.
 static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                         const uint64_t* d_in_sizes, int16_t* d_samples, const uint64_t* d_sample_offsets,
+                         const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
                          const uint32_t* d_sample_counts, int32_t* d_status, void* stream, uint32_t capCall)
 {
     HIPCHK(hipSetDevice(c->device));
@@ -2607,7 +2734,7 @@ static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8
     a.in = d_in;
     a.inOffsets = d_in_offsets;
     a.inSizes = d_in_sizes;
-    a.samples = d_samples;
+    set_out(a, d_samples);
     a.sampleOffsets = d_sample_offsets;
     a.sampleCounts = d_sample_counts;
     a.status = d_status;
@@ -2674,10 +2801,7 @@ static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8
             HIPCHK(hipStreamWaitEvent(c->mergeS, c->evDHuf[b], 0));
             ms = c->mergeS;
         }
-        if (codec == kCodecVbz) hipLaunchKernelGGL(vbz_merge_kernel, dim3((unsigned)G), dim3(64), 0, ms, a);
-        else if (a.lookback)  // few chunks: kMergeRanges single-wave workgroups per chunk
-            hipLaunchKernelGGL(dec_merge_lb_kernel, dim3((unsigned)(G * kMergeRanges)), dim3(64), 0, ms, a);
-        else hipLaunchKernelGGL(dec_merge_kernel, dim3((unsigned)G), dim3(64), 0, ms, a);
+        launch_merge(codec, a, G, ms);
         if (passes > 1) HIPCHK(hipEventRecord(c->evDFree[b], ms));
     }
     HIPCHK(hipGetLastError());
@@ -2832,7 +2956,7 @@ static int launch_large_encode(pgn_ctx* c, int codec, uint32_t count, uint32_t m
 }
 
 static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t maxN, const uint8_t* d_in,
-                               const uint64_t* d_in_offsets, const uint64_t* d_in_sizes, int16_t* d_samples,
+                               const uint64_t* d_in_offsets, const uint64_t* d_in_sizes, const DecOut& d_samples,
                                const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts, int32_t* d_status,
                                hipStream_t s)
 {
@@ -2847,7 +2971,7 @@ static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t m
     a.in = d_in;
     a.inOffsets = d_in_offsets;
     a.inSizes = d_in_sizes;
-    a.samples = d_samples;
+    set_out(a, d_samples);
     a.sampleOffsets = d_sample_offsets;
     a.sampleCounts = d_sample_counts;
     a.status = d_status;
@@ -2867,7 +2991,7 @@ static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t m
 // large pass (ordered after it on the stream).
 static int launch_claims_decode(pgn_ctx* c, int codec, uint32_t count, uint64_t maxSum, const uint32_t* list,
                                 const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_sizes,
-                                int16_t* d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts,
+                                const DecOut& d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts,
                                 int32_t* d_status, hipStream_t s)
 {
     const uint64_t cap = (maxSum < kClaimPassMax ? maxSum : kClaimPassMax) + kVbzPadding;
@@ -2881,7 +3005,7 @@ static int launch_claims_decode(pgn_ctx* c, int codec, uint32_t count, uint64_t 
     a.in = d_in;
     a.inOffsets = d_in_offsets;
     a.inSizes = d_in_sizes;
-    a.samples = d_samples;
+    set_out(a, d_samples);
     a.sampleOffsets = d_sample_offsets;
     a.sampleCounts = d_sample_counts;
     a.status = d_status;
@@ -2900,7 +3024,7 @@ static int launch_claims_decode(pgn_ctx* c, int codec, uint32_t count, uint64_t 
 // (the device arrays describe the same chunks); then the pass runs and the call waits for it.
 static int claims_from_host(pgn_ctx* c, int codec, size_t n, const int32_t* status, const uint32_t* counts,
                             const uint8_t* const* blobs, const uint64_t* blobLens, const uint8_t* d_in,
-                            const uint64_t* d_in_offsets, const uint64_t* d_in_sizes, int16_t* d_samples,
+                            const uint64_t* d_in_offsets, const uint64_t* d_in_sizes, const DecOut& d_samples,
                             const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts, int32_t* d_status,
                             hipStream_t s)
 {
@@ -2963,7 +3087,7 @@ static int launch_encode(pgn_ctx* c, int codec, size_t nchunks, const int16_t* d
 }
 
 static int launch_decode(pgn_ctx* c, int codec, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                         const uint64_t* d_in_sizes, int16_t* d_samples, const uint64_t* d_sample_offsets,
+                         const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
                          const uint32_t* d_sample_counts, int32_t* d_status, void* stream, uint32_t maxHint)
 {
     HIPCHK(hipSetDevice(c->device));
@@ -3015,10 +3139,10 @@ static int compress_batch(int codec, pgn_ctx* c, size_t nchunks, const int16_t* 
 }
 
 static int decompress_batch(int codec, pgn_ctx* c, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                            const uint64_t* d_in_sizes, int16_t* d_samples, const uint64_t* d_sample_offsets,
+                            const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
                             const uint32_t* d_sample_counts, int32_t* d_status, void* stream, uint32_t maxHint = 0)
 {
-    if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_samples || !d_sample_offsets || !d_sample_counts || !d_status)
+    if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_samples.p || !d_sample_offsets || !d_sample_counts || !d_status)
         return PGN_ERR_INVALID_ARG;
     if (nchunks == 0) return PGN_OK;
     std::lock_guard<std::mutex> g(c->mu);
@@ -3119,6 +3243,23 @@ int pgn_variant_decompress_batch_device(pgn_ctx* c, int variant, size_t nchunks,
 static int bounded_codec(int codec)
 {
     return codec == PGN_POD5_CODEC_VBZ ? (int)kCodecVbz : variant_codec(codec);
+}
+
+extern "C" int pgn_decompress_batch_device_pa(pgn_ctx* c, int codec, uint32_t max_chunk_samples, size_t nchunks,
+                                              const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_sizes,
+                                              void* d_out, int out_type, const uint64_t* d_out_offsets,
+                                              const uint32_t* d_sample_counts, const float* d_cal_offset,
+                                              const float* d_cal_scale, int32_t* d_status, void* stream)
+{
+    const int k = bounded_codec(codec);
+    if (!c || k < 0) return PGN_ERR_INVALID_ARG;
+    if (out_type != PGN_OUT_INT16 && out_type != PGN_OUT_F32 && out_type != PGN_OUT_F16) return PGN_ERR_INVALID_ARG;
+    if (out_type != PGN_OUT_INT16 && (!d_cal_offset || !d_cal_scale)) return PGN_ERR_INVALID_ARG;
+    // max_chunk_samples == 0: no bound (the unbounded calls, with their host wait), not a bound of 1
+    const DecOut out(d_out, out_type, out_type == PGN_OUT_INT16 ? nullptr : d_cal_offset,
+                     out_type == PGN_OUT_INT16 ? nullptr : d_cal_scale);
+    return decompress_batch(k, c, nchunks, d_in, d_in_offsets, d_in_sizes, out, d_out_offsets, d_sample_counts, d_status,
+                            stream, max_chunk_samples);
 }
 
 int pgn_compress_batch_bounded(pgn_ctx* c, int codec, uint32_t max_samples, size_t nchunks, const int16_t* d_samples,

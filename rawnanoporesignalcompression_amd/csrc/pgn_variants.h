@@ -50,27 +50,18 @@ __device__ __forceinline__ void load_deltas16(const int16_t* __restrict__ x, uin
     }
 }
 
-// the lane's 16 running sums (o[m], acc = o[15]) -> samples: wave scan for the carry, then stores
-template <bool Full>
+// the lane's 16 running sums (o[m], acc = o[15]) -> samples: wave scan for the carry, then the sample sink
+template <bool Full, class T>
 __device__ __forceinline__ void store_samples16(const uint32_t o[16], uint32_t acc, uint32_t& carry,
-                                                int16_t* __restrict__ out, uint32_t t, uint32_t n)
+                                                T* __restrict__ out, uint32_t t, uint32_t n, Cal cal)
 {
-    const uint32_t lane = (uint32_t)lane_id();
     const uint32_t incl = wave_incl_sum(acc);
     const uint32_t base = carry + incl - acc;
     carry += readlane_u32(incl, 63);
     uint32_t w[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) w[k] = ((o[2 * k] + base) & 0xFFFFu) | ((o[2 * k + 1] + base) << 16);
-    int16_t* dst = out + t + 16u * lane;
-    if (Full) {
-        gst<uint4>(dst, make_uint4(w[0], w[1], w[2], w[3]));
-        gst<uint4>(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
-    } else {
-#pragma unroll
-        for (int m = 0; m < 16; m++)
-            if (t + 16u * lane + (uint32_t)m < n) gst<uint16_t>(dst + m, (uint16_t)(w[m >> 1] >> (16 * (m & 1))));
-    }
+    sink_samples16<false>(out, w, t, n, Full, cal);
 }
 
 // number of valid samples of the lane in a step
@@ -153,9 +144,9 @@ __device__ __forceinline__ void c23_split_wave(const int16_t* __restrict__ x, ui
 // C2 / C3 merge over the concatenated intermediate: keys at 0, A at keys_length, then (C3) B at
 // + dA and H at + dA + dB, or (C2) H at + dA.  A read past `total` is the reference's UB -> 1.
 // *consumed = one past the last H byte (decode_scalar_lh / _ll_lh return data_h).
-template <bool C3>
+template <bool C3, class T = int16_t>
 __device__ __forceinline__ int c23_merge_wave(const uint8_t* __restrict__ in, uint64_t total, uint64_t dA, uint64_t dB,
-                                              int16_t* __restrict__ out, uint32_t n, uint64_t* consumed)
+                                              T* __restrict__ out, uint32_t n, uint64_t* consumed, Cal cal = Cal{0.f, 0.f})
 {
     const uint32_t lane = (uint32_t)lane_id();
     const uint64_t nk = svb_key_length(n);
@@ -205,8 +196,8 @@ __device__ __forceinline__ int c23_merge_wave(const uint8_t* __restrict__ in, ui
             acc += (uint32_t)zz_dec16((uint16_t)v);
             o[m] = acc;
         }
-        if (full) store_samples16<true>(o, acc, carry, out, t, n);
-        else store_samples16<false>(o, acc, carry, out, t, n);
+        if (full) store_samples16<true>(o, acc, carry, out, t, n, cal);
+        else store_samples16<false>(o, acc, carry, out, t, n, cal);
         if (C3) {
             pa += ts;
             pb += tb;
@@ -284,8 +275,9 @@ struct Vbz0MergeLds {
     alignas(16) uint8_t D[2 * kSplitStep + 64];
 };
 
-__device__ __forceinline__ int vbz0_merge_wave(const uint8_t* __restrict__ in, uint64_t total, int16_t* __restrict__ out,
-                                               uint32_t n, uint64_t* consumed, Vbz0MergeLds& W)
+template <class T = int16_t>
+__device__ __forceinline__ int vbz0_merge_wave(const uint8_t* __restrict__ in, uint64_t total, T* __restrict__ out,
+                                               uint32_t n, uint64_t* consumed, Vbz0MergeLds& W, Cal cal = Cal{0.f, 0.f})
 {
     const uint32_t lane = (uint32_t)lane_id();
     if (n == 0) {
@@ -333,8 +325,8 @@ __device__ __forceinline__ int vbz0_merge_wave(const uint8_t* __restrict__ in, u
             acc += (uint32_t)zz_dec16((uint16_t)v);
             o[m] = acc;
         }
-        if (full) store_samples16<true>(o, acc, carry, out, t, n);
-        else store_samples16<false>(o, acc, carry, out, t, n);
+        if (full) store_samples16<true>(o, acc, carry, out, t, n, cal);
+        else store_samples16<false>(o, acc, carry, out, t, n, cal);
         nib += tn;
         lds_sync();
     }

@@ -110,11 +110,10 @@ struct VbzMergeLds {
     alignas(16) uint8_t D[2 * kSplitStep + 32];
 };
 
-template <bool Full>
+template <bool Full, class T>
 __device__ __forceinline__ void vbz_merge_step(const VbzMergeLds& W, uint32_t kw, uint32_t q, uint32_t& carry,
-                                               int16_t* __restrict__ out, uint32_t t, uint32_t n)
+                                               T* __restrict__ out, uint32_t t, uint32_t n, Cal cal)
 {
-    const uint32_t lane = (uint32_t)lane_id();
     uint32_t acc = 0;
     uint32_t o[16];
 #pragma unroll
@@ -132,19 +131,12 @@ __device__ __forceinline__ void vbz_merge_step(const VbzMergeLds& W, uint32_t kw
     uint32_t w[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) w[k] = ((o[2 * k] + base) & 0xFFFFu) | ((o[2 * k + 1] + base) << 16);
-    int16_t* dst = out + t + 16u * lane;
-    if (Full) {
-        gst<uint4>(dst, make_uint4(w[0], w[1], w[2], w[3]));
-        gst<uint4>(dst + 8, make_uint4(w[4], w[5], w[6], w[7]));
-    } else {
-#pragma unroll
-        for (int m = 0; m < 16; m++)
-            if (t + 16u * lane + (uint32_t)m < n) gst<uint16_t>(dst + m, (uint16_t)(w[m >> 1] >> (16 * (m & 1))));
-    }
+    sink_samples16<false>(out, w, t, n, Full, cal);
 }
 
-__device__ __forceinline__ int vbz_merge_wave(const uint8_t* __restrict__ in, uint64_t total, int16_t* __restrict__ out,
-                                              uint32_t n, uint64_t* consumed, VbzMergeLds& W)
+template <class T = int16_t>
+__device__ __forceinline__ int vbz_merge_wave(const uint8_t* __restrict__ in, uint64_t total, T* __restrict__ out,
+                                              uint32_t n, uint64_t* consumed, VbzMergeLds& W, Cal cal = Cal{0.f, 0.f})
 {
     const uint32_t lane = (uint32_t)lane_id();
     if (n == 0) {
@@ -175,8 +167,8 @@ __device__ __forceinline__ int vbz_merge_wave(const uint8_t* __restrict__ in, ui
         const uint64_t w0 = stage_bytes(W.D, in, dpos, tot);
         lds_sync();
         const uint32_t q = (uint32_t)(dpos - w0) + incl - cnt;
-        if (full) vbz_merge_step<true>(W, kw, q, carry, out, t, n);
-        else vbz_merge_step<false>(W, kw, q, carry, out, t, n);
+        if (full) vbz_merge_step<true>(W, kw, q, carry, out, t, n, cal);
+        else vbz_merge_step<false>(W, kw, q, carry, out, t, n, cal);
         dpos += tot;
         lds_sync();
     }

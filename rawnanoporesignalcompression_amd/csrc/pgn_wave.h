@@ -42,6 +42,7 @@ __device__ __forceinline__ uint64_t uni(uint64_t v)
     return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
 }
 __device__ __forceinline__ long uni(long v) { return (long)uni((uint64_t)v); }
+__device__ __forceinline__ float uni(float v) { return __uint_as_float(uni(__float_as_uint(v))); }
 template <class T>
 __device__ __forceinline__ T* uni(T* p)
 {
