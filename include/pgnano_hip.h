@@ -235,8 +235,8 @@ int pgn_variant_decompress_batch_device(pgn_ctx *ctx, int variant, size_t nchunk
  * A NULL ctx, an unknown codec or out_type, or a missing calibration array is PGN_ERR_INVALID_ARG
  * before any GPU call.
  * Not covered: the host-memory per-chunk calls and pgn_pod5_decompress_rows (link-bound; calibrating
- * on the host is one line there), reading the calibration out of a POD5 reads table, normalisation,
- * bfloat16. */
+ * on the host is one line there), reading the calibration out of a POD5 reads table, bfloat16.
+ * Per-read normalisation is the next section. */
 typedef enum pgn_out_type { PGN_OUT_INT16 = 0, PGN_OUT_F32 = 1, PGN_OUT_F16 = 2 } pgn_out_type;
 
 int pgn_decompress_batch_device_pa(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nchunks,
@@ -244,6 +244,81 @@ int pgn_decompress_batch_device_pa(pgn_ctx *ctx, int codec, uint32_t max_chunk_s
                                    void *d_out, int out_type, const uint64_t *d_out_offsets,
                                    const uint32_t *d_sample_counts, const float *d_cal_offset,
                                    const float *d_cal_scale, int32_t *d_status, void *stream);
+
+/* ---- Per-read normalised output (quantile, med/MAD) -------------------------------------------
+ * A basecaller front end normalises each read by its own robust statistics: (x - centre) / spread,
+ * usually stored as binary16.  The statistics need the whole read and a read spans several chunks, so
+ * these calls work on reads.  Everything is exact: the order statistics are integers, the float steps
+ * are listed operation by operation.
+ * For a read with samples x[0..n) (its chunks concatenated in order) and s = sort(x) ascending:
+ *   rank statistic   q(p) = s[k], k = floor(p * (double)(n - 1)): one binary64 multiply, then floor
+ *                    (this formula, not numpy.quantile's virtual index)
+ *   median, doubled  m2 = s[(n-1)/2] + s[n/2];  med = 0.5f * (float)m2 (exact)
+ *   MAD, quadrupled  d_i = |2 x_i - m2|, t = sort(d), mad4 = t[(n-1)/2] + t[n/2];  MAD = 0.25f * (float)mad4
+ *                    (numpy's median(x) and median(abs(x - median(x))) in float64)
+ *   PGN_NORM_QUANTILE  a = q(p_lo), b = q(p_hi);  centre = centre_mult * (float)(a + b);
+ *                      spread = spread_mult * (float)(b - a)   (p_lo, p_hi, centre_mult, spread_mult used)
+ *   PGN_NORM_MEDMAD    centre = med;  spread = spread_mult * MAD   (spread_mult used; p and centre_mult
+ *                      are still validated)
+ *   both               spread = spread_floor where spread < spread_floor
+ *   output             inv = 1.0f / spread (one IEEE division);  out32 = ((float)adc + (-centre)) * inv --
+ *                      the pA formula above with offset = -centre and scale = inv (two roundings, no FMA);
+ *                      PGN_OUT_F16 is that value converted once, round to nearest even
+ * The multipliers are the caller's (usual: p 0.2 / 0.9 with 0.51 / 0.53, or 1.4826 for the MAD); the C ABI
+ * has no defaults.  Statistics are taken on ADC counts; for a positive calibration scale the normalised
+ * value equals the one taken on pA, and centre / spread are returned so a caller can map them to pA.
+ * n == 0: nothing is written; every stats field is 0 except spread = 1.  n >= 2^32: the read's status is
+ * PGN_ERR_UNSUPPORTED (n is reported, the other fields as for n == 0).  Fields the mode does not use are 0.
+ * Both calls return PGN_ERR_INVALID_ARG before any GPU call, checking in this order: a NULL ctx or
+ * params; an unknown mode (and, for the decode, codec or out_type, PGN_OUT_INT16 included); p outside
+ * [0, 1], NaN or p_lo > p_hi; a non-finite multiplier; spread_floor not > 0; then missing arrays. */
+typedef enum pgn_norm_mode { PGN_NORM_QUANTILE = 0, PGN_NORM_MEDMAD = 1 } pgn_norm_mode;
+typedef struct pgn_norm_params {
+    int32_t mode;  /* pgn_norm_mode */
+    int32_t pad;
+    double p_lo, p_hi;
+    float centre_mult, spread_mult, spread_floor, pad2;
+} pgn_norm_params;
+typedef struct pgn_read_stats {
+    uint64_t n;
+    int32_t status;
+    int16_t q_lo, q_hi;
+    int32_t m2;
+    uint32_t mad4;
+    float centre, spread;
+} pgn_read_stats;
+
+/* Statistics of reads already decoded on the device: read r = d_samples[d_read_offsets[r] .. +
+ * d_read_counts[r]) (elements; a read may start on any 2-byte boundary) -> d_stats[r]. */
+int pgn_read_stats_device(pgn_ctx *ctx, size_t nreads, const int16_t *d_samples, const uint64_t *d_read_offsets,
+                          const uint64_t *d_read_counts, const pgn_norm_params *params, pgn_read_stats *d_stats,
+                          void *stream);
+
+/* Decode the chunks of nreads reads and write each read normalised and contiguous.
+ *   codec, max_chunk_samples   as for pgn_decompress_batch_device_pa (0 = no bound)
+ *   d_read_first_chunk         nreads + 1 entries: read r owns chunks [first[r], first[r+1]) of the
+ *                              nchunks chunks, which are in read order (first[nreads] == nchunks)
+ *   d_out, out_type            PGN_OUT_F32 or PGN_OUT_F16; read r occupies [d_read_out_offsets[r], + n_r)
+ *                              elements, chunk c of it starting after the read's earlier chunks
+ *   d_adc                      optional: receives the raw samples at the same element offsets.  Without it
+ *                              PGN_OUT_F16 decodes into d_out and converts in place; PGN_OUT_F32 needs it
+ *                              (PGN_ERR_INVALID_ARG: the host cannot size a workspace without a wait)
+ *   d_stats                    optional: nreads entries
+ * Sequence: a small kernel expands reads to chunks (into context scratch, never read by the host), the
+ * int16 decode runs unchanged, then the statistics kernels, then one elementwise pass.  Asynchronous on
+ * `stream`, with no host wait beyond the unbounded decode's own.  d_chunk_status[c] is what the int16
+ * call gives; a read's status is its first chunk status that is not PGN_OK, in chunk order, and the
+ * output and stats of such a read are unspecified.  Nothing is written outside
+ * [d_read_out_offsets[r], + n_r) of any read.
+ * Not covered: reading the read -> chunk map out of a POD5 reads table, adapter trimming, bfloat16,
+ * the host-memory per-chunk calls, a read shared by several workgroups (one workgroup selects one read). */
+int pgn_decompress_reads_device_norm(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nreads,
+                                     size_t nchunks, const uint64_t *d_read_first_chunk, const uint8_t *d_in,
+                                     const uint64_t *d_in_offsets, const uint64_t *d_in_sizes,
+                                     const uint32_t *d_sample_counts, void *d_out, int out_type,
+                                     const uint64_t *d_read_out_offsets, int16_t *d_adc,
+                                     const pgn_norm_params *params, pgn_read_stats *d_stats,
+                                     int32_t *d_chunk_status, void *stream);
 
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->

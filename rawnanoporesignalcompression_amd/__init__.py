@@ -10,12 +10,15 @@ from .codec import (
     PGNanoCodec,
     PGNanoError,
     Pod5SignalBatch,
+    ReadStats,
     VBZCodec,
     calibrate_signal,
     compress_signal,
     compressed_signal_max_size,
     decompress_signal,
     default_codec,
+    norm_params,
+    normalise_signal,
     pinanoraw_compress_signal,
     vbz_compress_signal_capi,
     vbz_compressed_signal_max_size,
@@ -29,6 +32,7 @@ __all__ = [
     "PGNanoCodec",
     "PGNanoError",
     "Pod5SignalBatch",
+    "ReadStats",
     "VBZCodec",
     "calibrate_signal",
     "compress_signal",
@@ -36,6 +40,8 @@ __all__ = [
     "decompress_signal",
     "default_codec",
     "load_native",
+    "norm_params",
+    "normalise_signal",
     "pinanoraw_compress_signal",
     "vbz_compress_signal_capi",
     "vbz_compressed_signal_max_size",

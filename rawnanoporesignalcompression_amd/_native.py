@@ -35,6 +35,23 @@ PGN_STATS_PER_CHUNK = 10
 # pgn_out_type: the element type of pgn_decompress_batch_device_pa's output
 PGN_OUT_INT16, PGN_OUT_F32, PGN_OUT_F16 = 0, 1, 2
 
+# pgn_norm_mode and the two structs of the per-read normalisation calls
+PGN_NORM_QUANTILE, PGN_NORM_MEDMAD = 0, 1
+NORM_MODES = {"quantile": PGN_NORM_QUANTILE, "medmad": PGN_NORM_MEDMAD}
+
+
+class NormParams(C.Structure):
+    """pgn_norm_params"""
+    _fields_ = [("mode", C.c_int32), ("pad", C.c_int32), ("p_lo", C.c_double), ("p_hi", C.c_double),
+                ("centre_mult", C.c_float), ("spread_mult", C.c_float), ("spread_floor", C.c_float), ("pad2", C.c_float)]
+
+
+class ReadStats(C.Structure):
+    """pgn_read_stats"""
+    _fields_ = [("n", C.c_uint64), ("status", C.c_int32), ("q_lo", C.c_int16), ("q_hi", C.c_int16), ("m2", C.c_int32),
+                ("mad4", C.c_uint32), ("centre", C.c_float), ("spread", C.c_float)]
+
+
 # every symbol include/pgnano_hip.h declares: (name, restype, argtypes)
 _VP, _SZ, _U64P, _U32P, _I32P = C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p
 SIGNATURES = [
@@ -70,6 +87,10 @@ SIGNATURES = [
      [_VP, C.c_int, _SZ, _VP, _U64P, _U64P, _VP, _U64P, _U32P, _I32P, _VP]),
     ("pgn_decompress_batch_device_pa", C.c_int,
      [_VP, C.c_int, C.c_uint32, _SZ, _VP, _U64P, _U64P, _VP, C.c_int, _U64P, _U32P, _VP, _VP, _I32P, _VP]),
+    ("pgn_read_stats_device", C.c_int, [_VP, _SZ, _VP, _U64P, _U64P, _VP, _VP, _VP]),
+    ("pgn_decompress_reads_device_norm", C.c_int,
+     [_VP, C.c_int, C.c_uint32, _SZ, _SZ, _U64P, _VP, _U64P, _U64P, _U32P, _VP, C.c_int, _U64P, _VP, _VP, _VP, _I32P,
+      _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

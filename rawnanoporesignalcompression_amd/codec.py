@@ -20,6 +20,8 @@ The batched device API (:meth:`PGNanoCodec.compress_batch` / :meth:`decompress_b
 device-resident torch tensors: one launch encodes or decodes every chunk of a batch.
 :meth:`PGNanoCodec.decompress_batch_pa` decodes straight to the calibrated signal a basecaller reads
 (float32 or float16 pA; :func:`calibrate_signal` is the same arithmetic on the host).
+:meth:`PGNanoCodec.decompress_reads_norm` decodes whole reads and writes each normalised by its own
+quantiles or median / MAD; :meth:`PGNanoCodec.read_stats` gives those statistics for decoded reads.
 """
 from __future__ import annotations
 
@@ -66,6 +68,14 @@ def calibrate_signal(adc, offset, scale, dtype=np.float32):
     return pa if np.dtype(dtype) == np.float32 else pa.astype(dtype)
 
 
+def normalise_signal(adc, centre, spread, dtype=np.float32):
+    """The normalised signal on the host, ``(adc + (-centre)) * (1 / spread)`` in float32: the int16
+    converted exactly, one float32 division for the reciprocal, one add, one multiply;
+    ``dtype=np.float16`` rounds that value once.  :meth:`PGNanoCodec.decompress_reads_norm` writes these bits."""
+    inv = np.float32(1.0) / np.float32(spread)
+    return calibrate_signal(adc, -np.float32(centre), inv, dtype)
+
+
 def _ptr(t) -> int:
     return t.data_ptr() if t is not None else 0
 
@@ -74,6 +84,43 @@ def _require_device(t, name: str, device: int) -> None:
     """The batch kernels dereference their data pointers on the GPU: a host tensor would fault."""
     if not t.is_cuda or t.device.index != device:
         raise ValueError(f"{name} must be a tensor on cuda:{device} (got {t.device})")
+
+
+class ReadStats:
+    """``pgn_read_stats`` of every read as named columns over one device tensor (``raw``: uint8,
+    nreads x 32, the C struct's bytes).  ``n`` int64, ``status`` int32, ``q_lo`` / ``q_hi`` int16, ``m2``
+    int32, ``mad4`` int32 (the uint32's bits; it stays below 2^18), ``centre`` / ``spread`` float32:
+    views, no copies.  :meth:`numpy` gives the same as a structured host array."""
+
+    DTYPE = np.dtype([("n", "<u8"), ("status", "<i4"), ("q_lo", "<i2"), ("q_hi", "<i2"), ("m2", "<i4"),
+                      ("mad4", "<u4"), ("centre", "<f4"), ("spread", "<f4")])
+    _COLS = {"n": ("int64", 0), "status": ("int32", 2), "q_lo": ("int16", 6), "q_hi": ("int16", 7), "m2": ("int32", 4),
+             "mad4": ("int32", 5), "centre": ("float32", 6), "spread": ("float32", 7)}
+
+    def __init__(self, raw):
+        self.raw = raw
+
+    def __len__(self):
+        return int(self.raw.shape[0])
+
+    def __getattr__(self, name):
+        import torch
+
+        if name in ReadStats._COLS:
+            t, col = ReadStats._COLS[name]
+            return self.raw.view(getattr(torch, t))[:, col]
+        raise AttributeError(name)
+
+    def numpy(self):
+        return self.raw.cpu().numpy().reshape(-1).view(ReadStats.DTYPE)
+
+
+def norm_params(mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0):
+    """``pgn_norm_params`` from Python values (the defaults live here; the C ABI has none)."""
+    if mode not in _native.NORM_MODES:
+        raise ValueError(f"mode must be one of {sorted(_native.NORM_MODES)} (got {mode!r})")
+    return _native.NormParams(_native.NORM_MODES[mode], 0, float(p[0]), float(p[1]), float(centre_mult),
+                              float(spread_mult), float(spread_floor), 0.0)
 
 
 @dataclass
@@ -336,6 +383,98 @@ class PGNanoCodec:
                 types[dtype], _ptr(so), _ptr(counts), _ptr(co), _ptr(cs), _ptr(status), ls.cuda_stream))
         caller.wait_stream(ls)
         return out, so, status
+
+    def read_stats(self, samples, read_offsets, read_counts, stream: int | None = None, **params) -> ReadStats:
+        """The robust statistics of reads already decoded on the device (pgn_read_stats_device): read r is
+        ``samples[read_offsets[r] : read_offsets[r] + read_counts[r]]`` (int16; any start).  params: ``mode``
+        ("quantile" | "medmad"), ``p``, ``centre_mult``, ``spread_mult``, ``spread_floor`` as in
+        :meth:`decompress_reads_norm`.  Exact: rank k = floor(p * (n - 1)) of the sorted read, the median and
+        the MAD as numpy gives them in float64."""
+        import torch
+
+        prm = norm_params(**params)
+        _require_device(samples, "samples", self.device)
+        if samples.dtype != torch.int16:
+            raise ValueError(f"samples must be int16 (got {samples.dtype})")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = samples.device
+            n = int(read_counts.numel())
+            ro = read_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            rc = read_counts.to(device=dev, dtype=torch.int64).contiguous()
+            raw = torch.zeros((n, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
+            _check(self._lib.pgn_read_stats_device(self._h, n, _ptr(samples), _ptr(ro), _ptr(rc), C.byref(prm),
+                                                   _ptr(raw), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return ReadStats(raw)
+
+    def decompress_reads_norm(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, *,
+                              mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0,
+                              dtype=None, out=None, read_out_offsets=None, adc=None, max_chunk_samples: int = 0,
+                              stream: int | None = None):
+        """Decode whole reads and write each normalised by its own statistics, contiguous; returns
+        (out, read_out_offsets, :class:`ReadStats`, chunk statuses).
+
+        The chunks are in read order and ``read_first_chunk`` (nreads + 1 entries) says which are whose: read r
+        owns chunks ``read_first_chunk[r] : read_first_chunk[r + 1]``.  mode "quantile": with a, b the
+        samples of rank ``floor(p * (n - 1))`` for ``p = (p_lo, p_hi)``, ``centre = centre_mult * (a + b)``
+        and ``spread = spread_mult * (b - a)``; mode "medmad": ``centre = median``, ``spread = spread_mult *
+        MAD``.  ``spread`` is at least ``spread_floor``; the output is ``(adc + (-centre)) * (1 / spread)``
+        in float32 (``dtype=torch.float32``), or that rounded once to float16 (the default).  Bit for bit
+        what :func:`normalise_signal` gives on the host.
+
+        out / read_out_offsets: the destination (of ``dtype``) and each read's first element in it (default:
+        packed).  adc: an int16 tensor that receives the raw samples at the same element offsets; without
+        it float16 is converted in place and float32 takes a workspace allocated here.  max_chunk_samples:
+        the caller's bound on the chunk sizes, 0 for none.  A read's ``status`` is its first failing chunk's."""
+        import torch
+
+        dtype = torch.float16 if dtype is None else dtype
+        types = {torch.float32: _native.PGN_OUT_F32, torch.float16: _native.PGN_OUT_F16}
+        if dtype not in types:
+            raise ValueError(f"dtype must be torch.float32 or torch.float16 (got {dtype})")
+        prm = norm_params(mode, p, centre_mult, spread_mult, spread_floor)
+        if int(max_chunk_samples) < 0:
+            raise ValueError("max_chunk_samples must be >= 0 (0: no bound)")
+        _require_device(blobs, "blobs", self.device)
+        nchunks = int(sample_counts.numel())
+        nreads = int(read_first_chunk.numel()) - 1
+        if nreads < 0:
+            raise ValueError("read_first_chunk needs nreads + 1 entries")
+        for t, name, want in ((out, "out", dtype), (adc, "adc", torch.int16)):
+            if t is not None:
+                _require_device(t, name, self.device)
+                if t.dtype != want:
+                    raise ValueError(f"{name} must have dtype {want} (got {t.dtype})")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = blobs.device
+            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
+            first = read_first_chunk.to(device=dev, dtype=torch.int64).contiguous()
+            ends = torch.zeros(nchunks + 1, dtype=torch.int64, device=dev)
+            ends[1:] = torch.cumsum(counts.to(torch.int64), 0)
+            if read_out_offsets is None:
+                ro = ends[first[:-1]].contiguous()  # packed: a read starts where its first chunk would
+            else:
+                ro = read_out_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            if out is None:
+                out = torch.empty(max(int(ends[-1].item()), 1), dtype=dtype, device=dev)
+            if adc is None and dtype == torch.float32:
+                work = torch.empty(out.numel(), dtype=torch.int16, device=dev)
+            else:
+                work = adc
+            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
+            status = torch.full((nchunks,), -1, dtype=torch.int32, device=dev)
+            raw = torch.zeros((nreads, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
+            _check(self._lib.pgn_decompress_reads_device_norm(
+                self._h, self._pa_codec, int(max_chunk_samples), nreads, nchunks, _ptr(first), _ptr(blobs), _ptr(bo),
+                _ptr(bs), _ptr(counts), _ptr(out), types[dtype], _ptr(ro), _ptr(work), C.byref(prm), _ptr(raw),
+                _ptr(status), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return out, ro, ReadStats(raw), status
 
     def synth_reads(self, nreads: int, samples_per_read, seed: int = 42, first_read: int = 0, read_stride: int = 1,
                     p_switch_q16: int = 6554, level_mean: int = 500, level_sd: int = 60, noise_sd: int = 12,

@@ -4,6 +4,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#define PGN_SELECT_HOST_ONLY
+#include "pgn_select.h"
 #include "zstd1_dec.h"
 #include "zstd1_model.h"
 
@@ -109,6 +111,37 @@ long long z1m_content_size(const uint8_t* src, size_t n)
     bool ok = false;
     uint64_t v = frame_content_size(src, n, &ok);
     return ok ? (long long)v : -1;
+}
+
+// The read statistics (pgn_select.h) over serially built histograms: the rank walk, the keys and the
+// integer -> float step the kernels run.  Returns 0, or -1 for parameters the C ABI rejects.
+int pgnm_read_stats(const int16_t* x, uint64_t n, const pgn_norm_params* prm, pgn_read_stats* out)
+{
+    if (!pgn::sel::params_valid(prm) || !out) return -1;
+    pgn::sel::host_read_stats(x, n, *prm, *out);
+    return 0;
+}
+
+// The two-level coarse walk alone: coarse[1024] and nranks (1 or 2) ranks -> bin and residual rank.
+int pgnm_locate(const uint32_t* coarse, const uint32_t* k, int nranks, uint32_t* bin, uint32_t* resid)
+{
+    using namespace pgn::sel;
+    uint32_t groups[kGroups] = {};
+    for (uint32_t b = 0; b < kCoarseBins; b++) groups[b / kGroupBins] += coarse[b];
+    if (nranks == 1) {
+        const uint32_t k1[1] = {k[0]};
+        Place p[1];
+        locate<1>(groups, coarse, k1, p);
+        bin[0] = p[0].bin; resid[0] = p[0].resid;
+    } else if (nranks == 2) {
+        const uint32_t k2[2] = {k[0], k[1]};
+        Place p[2];
+        locate<2>(groups, coarse, k2, p);
+        for (int i = 0; i < 2; i++) { bin[i] = p[i].bin; resid[i] = p[i].resid; }
+    } else {
+        return -1;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include "../../include/pgnano_pod5.h"
 #include "pgn_c5.h"
 #include "pgn_internal.h"
+#include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
 #include "pgn_zdec.h"
@@ -2112,6 +2113,13 @@ struct pgn_ctx {
     size_t largeEpochSlots = 0;
     uint8_t* largeDecScratch = nullptr;
     size_t largeDecScratchBytes = 0;
+    // pgn_decompress_reads_device_norm: the reads expanded to chunks (per chunk: output offset and
+    // read; per read: n and, when the caller passes no d_stats, the statistics)
+    uint64_t* normChunkOut = nullptr;
+    uint32_t* normChunkRead = nullptr;
+    uint64_t* normReadN = nullptr;
+    pgn_read_stats* normStats = nullptr;
+    size_t normChunks = 0, normReads = 0;
     std::mutex mu;
     // combined per-chunk host calls (PcArena): pcOpen = the arena new calls join (-1: none idle)
     std::mutex pcMu;
@@ -2290,6 +2298,10 @@ int pgn_ctx_destroy(pgn_ctx* c)
     (void)hipFree(c->largeScratch);
     (void)hipFree(c->largeEpochs);
     (void)hipFree(c->largeDecScratch);
+    (void)hipFree(c->normChunkOut);
+    (void)hipFree(c->normChunkRead);
+    (void)hipFree(c->normReadN);
+    (void)hipFree(c->normStats);
     if (c->largeHdrHost) (void)hipHostFree(c->largeHdrHost);
     for (hipEvent_t e : {c->evScanFork, c->evScan})
         if (e) (void)hipEventDestroy(e);
@@ -3260,6 +3272,118 @@ extern "C" int pgn_decompress_batch_device_pa(pgn_ctx* c, int codec, uint32_t ma
                      out_type == PGN_OUT_INT16 ? nullptr : d_cal_scale);
     return decompress_batch(k, c, nchunks, d_in, d_in_offsets, d_in_sizes, out, d_out_offsets, d_sample_counts, d_status,
                             stream, max_chunk_samples);
+}
+
+// ---- per-read statistics and normalised output (pgn_select.h) -----------------------------------
+static int ensure_norm(pgn_ctx* c, size_t nreads, size_t nchunks)
+{
+    if (nchunks > c->normChunks) {
+        wait_last_host(c);
+        (void)hipFree(c->normChunkOut);
+        (void)hipFree(c->normChunkRead);
+        c->normChunkOut = nullptr;
+        c->normChunkRead = nullptr;
+        c->normChunks = 0;
+        HIPCHK(hipMalloc(&c->normChunkOut, nchunks * sizeof(uint64_t)));
+        HIPCHK(hipMalloc(&c->normChunkRead, nchunks * sizeof(uint32_t)));
+        c->normChunks = nchunks;
+    }
+    if (nreads > c->normReads) {
+        wait_last_host(c);
+        (void)hipFree(c->normReadN);
+        (void)hipFree(c->normStats);
+        c->normReadN = nullptr;
+        c->normStats = nullptr;
+        c->normReads = 0;
+        HIPCHK(hipMalloc(&c->normReadN, nreads * sizeof(uint64_t)));
+        HIPCHK(hipMalloc(&c->normStats, nreads * sizeof(pgn_read_stats)));
+        c->normReads = nreads;
+    }
+    return PGN_OK;
+}
+
+// the two statistics kernels: reads above sel::kShortMax samples one workgroup each, the others one wave each
+static int launch_read_stats(pgn_ctx* c, const sel::StatsArgs& a, hipStream_t s)
+{
+    const size_t cus = (size_t)(c->numCUs > 0 ? c->numCUs : 1);
+    const size_t longGrid = std::min<size_t>(a.nreads, cus * 4);
+    hipLaunchKernelGGL(sel::read_stats_kernel, dim3((unsigned)longGrid), dim3(sel::kSelThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    const size_t shortGrid = std::min<size_t>((a.nreads + 3) / 4, cus * 8);
+    hipLaunchKernelGGL(sel::read_stats_short_kernel, dim3((unsigned)shortGrid), dim3(sel::kSelThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+extern "C" int pgn_read_stats_device(pgn_ctx* c, size_t nreads, const int16_t* d_samples, const uint64_t* d_read_offsets,
+                                     const uint64_t* d_read_counts, const pgn_norm_params* params,
+                                     pgn_read_stats* d_stats, void* stream)
+{
+    if (!c || !sel::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if (!d_samples || !d_read_offsets || !d_read_counts || !d_stats) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    const sel::StatsArgs a{d_samples, d_read_offsets, d_read_counts, nreads, *params, d_stats, nullptr, nullptr};
+    const int rc = launch_read_stats(c, a, s);
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return rc;
+}
+
+extern "C" int pgn_decompress_reads_device_norm(pgn_ctx* c, int codec, uint32_t max_chunk_samples, size_t nreads,
+                                                size_t nchunks, const uint64_t* d_read_first_chunk, const uint8_t* d_in,
+                                                const uint64_t* d_in_offsets, const uint64_t* d_in_sizes,
+                                                const uint32_t* d_sample_counts, void* d_out, int out_type,
+                                                const uint64_t* d_read_out_offsets, int16_t* d_adc,
+                                                const pgn_norm_params* params, pgn_read_stats* d_stats,
+                                                int32_t* d_chunk_status, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    const int k = bounded_codec(codec);
+    if ((params->mode != PGN_NORM_QUANTILE && params->mode != PGN_NORM_MEDMAD) || k < 0 ||
+        (out_type != PGN_OUT_F32 && out_type != PGN_OUT_F16))
+        return PGN_ERR_INVALID_ARG;
+    if (!sel::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if (!d_read_first_chunk || !d_out || !d_read_out_offsets) return PGN_ERR_INVALID_ARG;
+    if (nchunks && (!d_in || !d_in_offsets || !d_in_sizes || !d_sample_counts || !d_chunk_status)) return PGN_ERR_INVALID_ARG;
+    if (out_type == PGN_OUT_F32 && !d_adc) return PGN_ERR_INVALID_ARG;  // no workspace the host could size
+    if (nreads == 0) return PGN_OK;
+    if (nreads > 0xFFFFFFFFull) return PGN_ERR_INVALID_ARG;  // the chunks' read index is 32-bit
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    int rc = ensure_norm(c, nreads, nchunks);
+    if (rc != PGN_OK) return rc;
+    hipLaunchKernelGGL(sel::expand_reads_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, s, (uint64_t)nreads,
+                       d_read_first_chunk, d_read_out_offsets, d_sample_counts, c->normChunkOut, c->normChunkRead,
+                       c->normReadN);
+    HIPCHK(hipGetLastError());
+    // the int16 decode, as the batch calls run it: into d_adc, or into the binary16 output itself
+    int16_t* adc = d_adc ? d_adc : (int16_t*)d_out;
+    if (nchunks)
+        rc = launch_decode(c, k, nchunks, d_in, d_in_offsets, d_in_sizes, DecOut(adc), c->normChunkOut, d_sample_counts,
+                           d_chunk_status, s, max_chunk_samples);
+    if (rc != PGN_OK) return rc;
+    pgn_read_stats* stats = d_stats ? d_stats : c->normStats;
+    const sel::StatsArgs a{adc, d_read_out_offsets, c->normReadN, nreads, *params, stats, nchunks ? d_chunk_status : nullptr,
+                           d_read_first_chunk};
+    rc = launch_read_stats(c, a, s);
+    if (rc == PGN_OK && nchunks) {
+        const sel::NormArgs na{adc, d_out, c->normChunkOut, d_sample_counts, c->normChunkRead, stats, nchunks};
+        const dim3 grid((unsigned)std::min<size_t>(nchunks, 1u << 20), sel::kNormSplit);
+        if (out_type == PGN_OUT_F32)
+            hipLaunchKernelGGL(sel::norm_convert_kernel<float>, grid, dim3(256), 0, s, na);
+        else
+            hipLaunchKernelGGL(sel::norm_convert_kernel<_Float16>, grid, dim3(256), 0, s, na);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return rc;
 }
 
 int pgn_compress_batch_bounded(pgn_ctx* c, int codec, uint32_t max_samples, size_t nchunks, const int16_t* d_samples,
