@@ -2572,7 +2572,7 @@ static int launch_encode_impl(pgn_ctx* c, int codec, size_t nchunks, const int16
         HIPCHK(hipStreamWaitEvent(c->side, c->evFork, 0));
     }
     const size_t bufBytes = G * (kChunkStreamBytes + kChunkFrameBytes + 2 * 4 * kStreams);
-    EncArgs a;
+    EncArgs a{};
     a.nchunks = nchunks;
     a.samples = d_samples;
     a.sampleOffsets = d_sample_offsets;

@@ -6,7 +6,9 @@
 //   * literal histograms (LDS atomics, one histogram per Huffman segment);
 //   * symbol ranking for the Huffman sort; per-segment bit counts;
 //   * Huffman bit packing (prefix sum of code lengths, LDS window, byte flush).
-// Serial stages (tree build, weight FSE, sequence FSE) run on lane 0 with the shared zstd1_* code.
+// Serial stages (tree build, table normalisation) run wave-uniform with the shared zstd1_* code; the
+// independent FSE state chains (two for the Huffman weights, three for a section of up to 64
+// sequences) run side by side on the first lanes.
 #pragma once
 #ifndef PGN_AB_SKIP
 #define PGN_AB_SKIP 0  // diagnostic builds (tools/ab_skip.sh): 1 no zstd stage, 2 search only, 3 no Huffman, 4 no bit packing, 5 tree only;
@@ -68,6 +70,10 @@ struct alignas(16) EncLds {
                     uint32_t wcount[16];  // weight histogram
                     int16_t wnorm[16];
                     uint32_t wcumul[16];
+                    // the weight-FSE chains (under the tree build's nodes, dead by now): each emission's
+                    // deltaNbBits / deltaFindState going in, its state | bit count << 16 coming out
+                    uint2 wpair[256];
+                    uint32_t wrec[256];
                 };
                 struct {  // encode (after the table description has left for HBM)
                     uint32_t win[kWinWords];  // output bit window
@@ -79,13 +85,21 @@ struct alignas(16) EncLds {
         };
         struct {  // sequences section (after the literals section is written)
             z1::FseCTable sct[3];  // ll, of, ml
-            uint8_t stsym[512];    // FSE spread scratch
-            uint32_t scount[3][64];
-            int16_t snorm[64];
-            uint32_t scumul[64];
-            uint8_t snc[128];      // normalized-count header staging
-            uint32_t sv[3][64];    // staged sequences: litLength, mlBase, offset
-            uint8_t sc[3][64];     //                   ll, of, ml codes
+            uint32_t scount[3][64];  // code histograms; then the one-batch path's output bit window
+            union {
+                struct {
+                    uint8_t stsym[512];    // FSE spread scratch
+                    int16_t snorm[64];
+                    uint32_t scumul[64];
+                    uint8_t snc[128];      // normalized-count header staging
+                    uint32_t sv[3][64];    // staged sequences: litLength, mlBase, offset
+                    uint8_t sc[3][64];     //                   ll, of, ml codes
+                };
+                // one batch (seq_section_one_batch_wave): per table and sequence, in stream order, the
+                // code's deltaNbBits / deltaFindState going into the state chain, state | bit count << 16
+                // (in x) coming out
+                uint2 spair[3][64];
+            };
         };
     };
     uint32_t u[8];
@@ -1200,12 +1214,16 @@ __device__ __forceinline__ void wfse_encode(z1::BitW& bw, uint32_t& st, const WC
 
 // HUF_writeCTable into L.hdr from L.nbBits (wave-uniform; weights and their histogram by ballots).
 // Returns the description size, 0 if it cannot be written (raw weights with > 128 symbols).
-__device__ __noinline__ uint32_t huf_write_ctable_wave(uint32_t maxSym, uint32_t huffLog, PhaseProf& P)
+// rawFrom: a description of this size or more sends the section raw whatever else it holds, so the
+// caller only needs to learn that much: 0 is returned as soon as the size is known to reach it, which
+// the description's own bounds often settle before its FSE chains run (~0u: always the exact size).
+__device__ __noinline__ uint32_t huf_write_ctable_wave(uint32_t maxSym, uint32_t huffLog, uint32_t rawFrom, PhaseProf& P)
 {
     EncLds& L = sEnc;
     const int lane = lane_id();
     maxSym = uni(maxSym);
     huffLog = uni(huffLog);
+    rawFrom = uni(rawFrom);
     const uint32_t wtSize = maxSym;  // weights of symbols 0 .. maxSym-1
     uint32_t w[4];
 #pragma unroll
@@ -1239,56 +1257,76 @@ __device__ __noinline__ uint32_t huf_write_ctable_wave(uint32_t maxSym, uint32_t
             if (z1::fse_normalize(L.wnorm, tableLog, L.wcount, wtSize, maxW, false)) {
                 lds_sync();
                 const size_t nh = z1::fse_write_ncount(L.hdr + 1, L.wnorm, maxW, tableLog);
-                if (nh && wtSize > 2) {
+                bool chain = nh && wtSize > 2;
+                if (chain) {
+                    // The description's size before its chains run.  An emission of a weight of
+                    // normalised count nv costs tableLog bits when nv is 1, else maxBitsOut - 1 or
+                    // maxBitsOut bits (exactly maxBitsOut - 1 for a power of two), so the size is at
+                    // least nh + the bytes of those minima over the emitted weights (all but the last
+                    // two, which start the states), the two state flushes and the end mark.  When that
+                    // already rejects the FSE form, or already reaches rawFrom, the outcome is decided.
+                    const uint32_t wl0 = L.weights[wtSize - 1], wl1 = L.weights[wtSize - 2];
+                    uint32_t mb = 0;
+                    if ((uint32_t)lane <= maxW) {
+                        const uint32_t c = L.wcount[lane] - (wl0 == (uint32_t)lane) - (wl1 == (uint32_t)lane);
+                        const int nv = L.wnorm[lane];
+                        mb = c * (nv <= 1 ? tableLog : tableLog - z1::highbit32((uint32_t)(nv - 1)) - 1u);
+                    }
+                    const uint32_t hLow = (uint32_t)nh + ((wave_sum(mb) + 2u * tableLog + 1u + 7u) >> 3);
+                    if (hLow >= maxSym / 2) {
+                        hSize = hLow;  // not the size, but like it too large for the FSE form
+                        chain = false;
+                    } else if (hLow + 1 >= rawFrom && (maxSym > 128 || (maxSym + 1) / 2 + 1 >= rawFrom)) {
+                        return 0;  // the FSE form and the raw weights are both too large, or cannot be written
+                    }
+                }
+                if (chain) {
                     fse_build_ctable_small(L.fct, L.wnorm, maxW, tableLog, L.fscratch, L.wcumul);
-                    // FSE_compress_usingCTable (two interleaved states) in two passes.  The states run
-                    // serially and wave-uniform (table entry u / symbol s in lane u / s, read with
-                    // v_readlane): chain X starts from the last weight, chain Y from the one before, and
-                    // emission k (k = 0 .. n - 3) encodes weight n - 3 - k on chain X (k even) or Y (k
-                    // odd); each emission only records its state and bit count into lane k & 63 of
-                    // rec[k >> 6] (the reference's bit-container flushes do not change the bit order).
-                    // Then the fields' offsets come from a wave prefix sum and their bits are ORed into
-                    // the description in LDS, so the serial loop carries no bit packing (it was ~26
-                    // scalar instructions per weight).
-                    const uint32_t vST = ((uint32_t)lane < (1u << tableLog)) ? (uint32_t)L.fct.stateTable[lane] : 0u;
-                    const uint32_t vDN = ((uint32_t)lane <= maxW) ? L.fct.deltaNbBits[lane] : 0u;
-                    const uint32_t vDF = ((uint32_t)lane <= maxW) ? (uint32_t)L.fct.deltaFindState[lane] : 0u;
-                    const uint32_t W4 = reinterpret_cast<const uint32_t*>(L.weights)[lane];
-                    auto wsym = [&](uint32_t i) -> uint32_t {
-                        return (readlane_u32(W4, (int)(i >> 2)) >> (8u * (i & 3u))) & 0xFFu;
-                    };
-                    auto init = [&](uint32_t sym) -> uint32_t {
-                        const uint32_t dn = readlane_u32(vDN, (int)sym), df = readlane_u32(vDF, (int)sym);
-                        const uint32_t nbo = (dn + (1u << 15)) >> 16;
-                        const uint32_t v = (nbo << 16) - dn;
-                        return readlane_u32(vST, (int)((v >> nbo) + df));
-                    };
+                    // FSE_compress_usingCTable (two interleaved states) in two passes.  Chain X starts
+                    // from the last weight, chain Y from the one before, and emission k (k = 0 .. n - 3)
+                    // encodes weight n - 3 - k on chain X (k even) or Y (k odd).  The two chains are
+                    // independent, so X runs on lane 0 and Y on lane 1 in the same vector instructions:
+                    // a step reads its emission's deltas (staged in LDS by emission, off the state
+                    // chain), reads the next state from the state table and records state | bit count
+                    // << 16 in wrec[k] (the reference's bit-container flushes do not change the bit
+                    // order).  Then the fields' offsets come from a wave prefix sum and their bits are
+                    // ORed into the description in LDS, so the serial loop carries no bit packing.  (The
+                    // chains used to run wave-uniform on the scalar unit through v_readlane /
+                    // v_writelane, ~14 scalar instructions per emission.)
                     const uint32_t n = wtSize, nEm = n - 2;
-                    // each emission's deltas, lane-parallel
-                    uint32_t dnR[4], dfR[4], rec[4];
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const uint32_t k = (uint32_t)lane + 64u * (uint32_t)r;
-                        const uint32_t sy = k < nEm ? (uint32_t)L.weights[n - 3 - k] : 0u;
-                        dnR[r] = L.fct.deltaNbBits[sy];
-                        dfR[r] = (uint32_t)L.fct.deltaFindState[sy];
-                        rec[r] = 0;
-                    }
-                    uint32_t stX = init(wsym(n - 1)), stY = init(wsym(n - 2));
-                    auto enc = [&](uint32_t& st, uint32_t& rc, uint32_t dv, uint32_t fv, uint32_t k) {
-                        const uint32_t dn = readlane_u32(dv, (int)(k & 63u)), df = readlane_u32(fv, (int)(k & 63u));
-                        const uint32_t nbo = (st + dn) >> 16;
-                        // (one SGPR read per VALU instruction on gfx950: the lane select goes through m0)
-                        asm volatile("v_writelane_b32 %0, %1, m0" : "+v"(rc) : "s"(st | (nbo << 16)), "{m0}"(k & 63u));
-                        st = readlane_u32(vST, (int)((st >> nbo) + df));
-                    };
-#pragma unroll
-                    for (uint32_t r = 0; r < 4; r++) {
-                        const uint32_t kEnd = nEm < 64u * r + 64u ? nEm : 64u * r + 64u;
-                        for (uint32_t k = 64u * r; k < kEnd; k += 2) {  // a pair never crosses a register
-                            enc(stX, rec[r], dnR[r], dfR[r], k);
-                            if (k + 1 < kEnd) enc(stY, rec[r], dnR[r], dfR[r], k + 1);
+                        if (k < nEm) {
+                            const uint32_t sy = L.weights[n - 3 - k];
+                            L.wpair[k] = make_uint2(L.fct.deltaNbBits[sy], 2u * (uint32_t)L.fct.deltaFindState[sy]);  // y: a byte offset
                         }
+                    }
+                    lds_sync();
+                    uint32_t st = 0;
+                    if (lane < 2) {
+                        const uint32_t sym = L.weights[n - 1 - (uint32_t)lane];
+                        const uint32_t dn0 = L.fct.deltaNbBits[sym], nbo0 = (dn0 + (1u << 15)) >> 16;
+                        st = L.fct.stateTable[(((nbo0 << 16) - dn0) >> nbo0) + (uint32_t)L.fct.deltaFindState[sym]];
+                        auto enc = [&](uint32_t k) {
+                            const uint2 d = L.wpair[k];
+                            const uint32_t nbo = (st + d.x) >> 16;
+                            L.wrec[k] = st | (nbo << 16);
+                            st = *(const uint16_t*)((const uint8_t*)L.fct.stateTable + (2u * (st >> nbo) + d.y));
+                        };
+                        const uint32_t nPair = uni(nEm >> 1);
+                        uint32_t k = (uint32_t)lane;
+#pragma unroll 4
+                        for (uint32_t i = 0; i < nPair; i++, k += 2) enc(k);
+                        if (k < nEm) enc(k);  // odd count: the last emission is chain X's
+                    }
+                    lds_sync();
+                    const uint32_t stX = readlane_u32(st, 0), stY = readlane_u32(st, 1);
+                    uint32_t rec[4];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const uint32_t k = (uint32_t)lane + 64u * (uint32_t)r;
+                        rec[r] = k < nEm ? L.wrec[k] : 0u;
                     }
                     // FSE_flushCState of the second state, then the first (even n: X then Y; odd n: Y
                     // then X), then the end mark
@@ -1465,6 +1503,137 @@ __global__ __launch_bounds__(64) void seq_default_ctables_kernel()
     }
 }
 
+// A section of up to 64 sequences whose three tables are predefined or RLE (all of them below 36
+// sequences: ZSTD_selectEncodingType), one lane per sequence and no loop over the sequences but the
+// state chains: lane j takes sequence nbSeq - 1 - j, the stream's j-th.  The three FSE chains are
+// independent, so they run on lanes 0 .. 2 in the same vector instructions, each step recording its
+// state and bit count; then every lane ORs its sequence's six bit fields into a window in LDS at the
+// offset a wave prefix sum gives it, and the window is copied out.  Only the predefined tables' state
+// tables are brought into LDS; the per-code deltas are gathered from the tables in global memory.
+// Returns the section's size, or kSeqNotOneBatch (nothing written) when a table would be compressed.
+constexpr size_t kSeqNotOneBatch = (size_t)-3;
+__device__ __noinline__ size_t seq_section_one_batch_wave(const uint32_t* sq, uint32_t nbSeq, uint8_t* dst)
+{
+    EncLds& L = sEnc;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t last = nbSeq - 1;
+    const bool act = lane < nbSeq;
+    uint32_t val[3] = {0, 0, 0}, code[3] = {0, 0, 0};  // litLength, offset, mlBase and their codes
+    if (act) {
+        const uint32_t t = last - lane;
+        val[0] = gld<uint32_t>(sq + 3 * t);
+        val[1] = gld<uint32_t>(sq + 3 * t + 1);
+        val[2] = gld<uint32_t>(sq + 3 * t + 2);
+        code[0] = z1::ll_code(val[0]);
+        code[1] = z1::highbit32(val[1]);
+        code[2] = z1::ml_code(val[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) L.scount[k][lane] = 0;
+    lds_sync();
+    if (act) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) atomicAdd(&L.scount[k][code[k]], 1u);
+    }
+    lds_sync();
+    const unsigned normLogs[3] = {z1::kLLDefaultNormLog, z1::kOFDefaultNormLog, z1::kMLDefaultNormLog};
+    uint32_t types[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t mostFrequent = wave_max(act ? L.scount[k][code[k]] : 0u);
+        const uint32_t mx = wave_max(code[k]);
+        types[k] = z1::select_encoding_type(mostFrequent, nbSeq, normLogs[k], k == 1 ? mx <= z1::kDefaultMaxOff : true);
+        if (types[k] == z1::kSetCompressed) return kSeqNotOneBatch;
+    }
+    lds_sync();  // the histograms are read: their storage becomes the bit window
+    lds_u32* win = (lds_u32*)&L.scount[0][0];
+#pragma unroll
+    for (int k = 0; k < 3; k++) win[lane + 64 * k] = 0;
+    uint8_t* op = dst + 2;  // after the count and the table-types byte
+    uint32_t tlog[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        uint2 d = make_uint2(0u, 0u);  // RLE: no state bits, state 0
+        if (types[k] == z1::kSetRle) {
+            if (lane == 0) {
+                gst<uint8_t>(op, (uint8_t)code[k]);
+                L.sct[k].stateTable[0] = 0;
+            }
+            op += 1;
+            tlog[k] = 0;
+        } else {  // the predefined table, built once (seq_default_ctables_kernel)
+            if (lane < 32) ((uint32_t*)L.sct[k].stateTable)[lane] = gld<uint32_t>((const uint32_t*)gSeqDefCT[k].stateTable + lane);
+            if (act) d = make_uint2(gld<uint32_t>(&gSeqDefCT[k].deltaNbBits[code[k]]), gld<uint32_t>(&gSeqDefCT[k].deltaFindState[code[k]]));
+            tlog[k] = normLogs[k];
+        }
+        if (act) L.spair[k][lane] = d;
+    }
+    if (lane == 0) {
+        gst<uint8_t>(dst, (uint8_t)nbSeq);
+        gst<uint8_t>(dst + 1, (uint8_t)((types[0] << 6) + (types[1] << 4) + (types[2] << 2)));
+    }
+    lds_sync();
+    // the chains: FSE_initCState2 on the last sequence's codes, then one FSE_encodeSymbol per sequence
+    uint32_t st = 0;
+    if (lane < 3) {
+        const uint16_t* tbl = L.sct[lane].stateTable;
+        const uint2 d0 = L.spair[lane][0];
+        const uint32_t nbo0 = (d0.x + (1u << 15)) >> 16;
+        st = tbl[(int32_t)(((nbo0 << 16) - d0.x) >> nbo0) + (int32_t)d0.y];
+        for (uint32_t j = 1; j <= last; j++) {
+            const uint2 d = L.spair[lane][j];
+            const uint32_t nbo = (st + d.x) >> 16;
+            L.spair[lane][j].x = st | (nbo << 16);
+            st = tbl[(int32_t)(st >> nbo) + (int32_t)d.y];
+        }
+    }
+    lds_sync();
+    // a sequence's fields in stream order: OF, ML, LL state bits (not the first: its codes start the
+    // states), then the extra bits of litLength, matchLength and the offset
+    uint32_t fv[6] = {0, 0, 0, val[0], val[2], val[1]}, fn[6] = {0, 0, 0, 0, 0, 0};
+    if (act) {
+        if (lane > 0) {
+            const uint32_t rOF = L.spair[1][lane].x, rML = L.spair[2][lane].x, rLL = L.spair[0][lane].x;
+            fv[0] = rOF & 0xFFFFu; fn[0] = rOF >> 16;
+            fv[1] = rML & 0xFFFFu; fn[1] = rML >> 16;
+            fv[2] = rLL & 0xFFFFu; fn[2] = rLL >> 16;
+        }
+        fn[3] = z1::ll_bits(code[0]);
+        fn[4] = z1::ml_bits(code[2]);
+        fn[5] = code[1];
+    }
+    const uint32_t mine = fn[0] + fn[1] + fn[2] + fn[3] + fn[4] + fn[5];
+    const uint32_t incl = wave_incl_sum(mine);
+    uint32_t pos = incl - mine;
+    auto put = [&](uint32_t at, uint32_t v, uint32_t nb) {
+        if (nb) {
+            v &= (uint32_t)((1ull << nb) - 1ull);
+            const uint32_t w = at >> 5, sh = at & 31u;
+            __hip_atomic_fetch_or(&win[w], v << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (sh + nb > 32u) __hip_atomic_fetch_or(&win[w + 1], v >> (32u - sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+    };
+#pragma unroll
+    for (int f = 0; f < 6; f++) {
+        put(pos, fv[f], fn[f]);
+        pos += fn[f];
+    }
+    // FSE_flushCState of ML, OF, LL, then the end mark
+    uint32_t tot = readlane_u32(incl, 63);
+    const uint32_t sLL = readlane_u32(st, 0), sOF = readlane_u32(st, 1), sML = readlane_u32(st, 2);
+    if (lane == 0) {
+        put(tot, sML, tlog[2]);
+        put(tot + tlog[2], sOF, tlog[1]);
+        put(tot + tlog[2] + tlog[1], sLL, tlog[0]);
+        put(tot + tlog[2] + tlog[1] + tlog[0], 1u, 1u);
+    }
+    tot += tlog[2] + tlog[1] + tlog[0] + 1u;
+    lds_sync();
+    const uint32_t bytes = (tot + 7) >> 3;
+    for (uint32_t b = lane; b < bytes; b += 64) gst<uint8_t>(op + b, (uint8_t)(win[b >> 2] >> (8u * (b & 3u))));
+    return (size_t)(op + bytes - dst);
+}
+
 __device__ __noinline__ size_t seq_section_wave(EncScratch S, uint32_t nbSeq)
 {
     EncLds& L = sEnc;
@@ -1479,6 +1648,10 @@ __device__ __noinline__ size_t seq_section_wave(EncScratch S, uint32_t nbSeq)
     uint8_t* ofC = S.codes + S.maxSeq;
     uint8_t* mlC = S.codes + 2 * S.maxSeq;
     const uint32_t* sq = (const uint32_t*)S.seqs;  // {litLength, offset, mlBase} per sequence
+    if (nbSeq >= 1 && nbSeq <= 64) {
+        const size_t r = seq_section_one_batch_wave(sq, nbSeq, dst);
+        if (r != kSeqNotOneBatch) return r;
+    }
     // number of sequences
     uint32_t hl;
     if (nbSeq < 128) {
@@ -1816,6 +1989,7 @@ __device__ __noinline__ LitOut compress_literals_wave(uint8_t* __restrict__ dst,
 #if PGN_AB_SKIP == 5  // diagnostic: stop after the tree (instruction attribution of the table description)
     { size_t r = write_raw_literals_wave(dst, lit, n); return ret(r + 0 * hl, false); }
 #endif
+    uint32_t rawFrom = ~0u;
     if (!repeat) {
         // the streams alone already miss the gain the section must make: raw literals whatever the
         // table description's size (HUF_compress_internal's final check), so it is not written
@@ -1833,8 +2007,10 @@ __device__ __noinline__ LitOut compress_literals_wave(uint8_t* __restrict__ dst,
             if (k == 0 || !single) cs += (wave_sum(b4[k]) + 8) >> 3;
         if (cs >= n - minGain) { size_t r = write_raw_literals_wave(dst, lit, n); P.mark(7); return ret(r, false); }
         if (lhSize + cs >= rawAt) { P.mark(7); return ret(lhSize + cs, false); }
+        // a new table's description of this size sends the section raw (the checks below)
+        rawFrom = n - minGain - cs < n - 12 ? n - minGain - cs : n - 12;
     }
-    hSize = huf_write_ctable_wave(maxSym, hl, P);
+    hSize = huf_write_ctable_wave(maxSym, hl, rawFrom, P);
     P.count(5);
     P.count(6, maxSym);
     P.mark(5);
