@@ -235,8 +235,8 @@ int pgn_variant_decompress_batch_device(pgn_ctx *ctx, int variant, size_t nchunk
  * A NULL ctx, an unknown codec or out_type, or a missing calibration array is PGN_ERR_INVALID_ARG
  * before any GPU call.
  * Not covered: the host-memory per-chunk calls and pgn_pod5_decompress_rows (link-bound; calibrating
- * on the host is one line there), reading the calibration out of a POD5 reads table, bfloat16.
- * Per-read normalisation is the next section. */
+ * on the host is one line there), bfloat16.  The calibration of a POD5 file's reads comes from
+ * pgn_pod5_reads_read (pgnano_pod5file.h).  Per-read normalisation is the next section. */
 typedef enum pgn_out_type { PGN_OUT_INT16 = 0, PGN_OUT_F32 = 1, PGN_OUT_F16 = 2 } pgn_out_type;
 
 int pgn_decompress_batch_device_pa(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nchunks,
@@ -310,8 +310,9 @@ int pgn_read_stats_device(pgn_ctx *ctx, size_t nreads, const int16_t *d_samples,
  * call gives; a read's status is its first chunk status that is not PGN_OK, in chunk order, and the
  * output and stats of such a read are unspecified.  Nothing is written outside
  * [d_read_out_offsets[r], + n_r) of any read.
- * Not covered: reading the read -> chunk map out of a POD5 reads table, adapter trimming, bfloat16,
- * the host-memory per-chunk calls, a read shared by several workgroups (one workgroup selects one read). */
+ * Not covered: adapter trimming, bfloat16, the host-memory per-chunk calls, a read shared by several
+ * workgroups (one workgroup selects one read).  The read -> chunk map of a POD5 file comes from
+ * pgn_pod5_reads_read, and pgn_pod5_load_reads_device (pgnano_pod5file.h) makes this call from a file. */
 int pgn_decompress_reads_device_norm(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nreads,
                                      size_t nchunks, const uint64_t *d_read_first_chunk, const uint8_t *d_in,
                                      const uint64_t *d_in_offsets, const uint64_t *d_in_sizes,
@@ -319,6 +320,33 @@ int pgn_decompress_reads_device_norm(pgn_ctx *ctx, int codec, uint32_t max_chunk
                                      const uint64_t *d_read_out_offsets, int16_t *d_adc,
                                      const pgn_norm_params *params, pgn_read_stats *d_stats,
                                      int32_t *d_chunk_status, void *stream);
+
+/* ---- Per-read calibrated output ------------------------------------------------------------------
+ * pgn_decompress_batch_device_pa for whole reads: the chunks are in read order, d_read_first_chunk and
+ * d_read_out_offsets as in the norm call above, and the calibration is per read (d_read_cal_offset[r],
+ * d_read_cal_scale[r]; ignored, may be NULL, for PGN_OUT_INT16 -- the device form of
+ * pod5_get_read_complete_signal, c_api.h:489-502).  A small kernel expands reads to chunks (output
+ * offset, offset and scale per chunk, into context scratch the host never reads), then the decode of
+ * pgn_decompress_batch_device_pa runs unchanged: the values are that call's, bit for bit.
+ * d_chunk_status[c] is what the int16 call gives.  d_read_status (optional, nreads entries) receives
+ * each read's first chunk status that is not PGN_OK, in chunk order; a read without chunks gets PGN_OK.
+ * PGN_ERR_INVALID_ARG before any GPU call, in the norm call's order: a NULL ctx; an unknown codec or
+ * out_type; then (for nreads > 0: with no reads the arrays have no entries and may be NULL) missing
+ * arrays.  No host wait beyond the unbounded decode's own. */
+int pgn_decompress_reads_device_pa(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nreads, size_t nchunks,
+                                   const uint64_t *d_read_first_chunk, const uint8_t *d_in,
+                                   const uint64_t *d_in_offsets, const uint64_t *d_in_sizes,
+                                   const uint32_t *d_sample_counts, void *d_out, int out_type,
+                                   const uint64_t *d_read_out_offsets, const float *d_read_cal_offset,
+                                   const float *d_read_cal_scale, int32_t *d_read_status, int32_t *d_chunk_status,
+                                   void *stream);
+
+/* The same per-read statuses for the callers of pgn_decompress_reads_device_norm (or of any batch
+ * decode whose chunks are in read order): d_read_status[r] = the first of
+ * d_chunk_status[first[r] .. first[r + 1]) that is not PGN_OK, else PGN_OK.  Asynchronous on `stream`,
+ * ordered after the context's earlier calls. */
+int pgn_reads_status_device(pgn_ctx *ctx, size_t nreads, const uint64_t *d_read_first_chunk,
+                            const int32_t *d_chunk_status, int32_t *d_read_status, void *stream);
 
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->

@@ -16,8 +16,11 @@
  * This header replaces the Arrow-based pieces of that path with a native reader and writer: the
  * footer and the Arrow IPC file format (flatbuffer schema, record batch and footer messages) are
  * parsed and written directly, so the signal column can be handed to the GPU codec without Arrow.
- * The other embedded tables are not interpreted: a writer given a source file copies them byte for
- * byte (what the reference's `copy` does to them when only the signal codec changes).
+ * Of the other embedded tables the reads table is read too (pgn_pod5_reads_*: which signal rows make
+ * which read, and each read's calibration), and pgn_pod5_load_reads_device puts whole reads in HBM
+ * from it.  The run-info table is not interpreted, and no table but the signal table is written from
+ * scratch: a writer given a source file copies the others byte for byte (what the reference's `copy`
+ * does to them when only the signal codec changes).
  *
  * pgn_pod5_transcode_file (GPU) is `copy in.pod5 out.pod5 --pgnano | --VBZ` for the signal table:
  * the rows are decoded and re-encoded by batched launches (pgnano_pod5.h's codecs) and written with
@@ -141,6 +144,73 @@ int pgn_pod5_write_file_keep_going(const char *path, const pgn_pod5_file *source
                                    const uint8_t *read_ids, const uint32_t *samples, const uint64_t *offsets,
                                    const uint8_t *data, const int32_t *row_status, uint32_t rows_per_batch,
                                    const uint8_t *section_marker, pgn_pod5_keep_going_result *res);
+
+/* ---- The reads table -----------------------------------------------------------------------------
+ * What the reference's reader gives through pod5_get_read_batch_row_info_data,
+ * pod5_get_signal_row_indices, pod5_get_read_complete_sample_count and pod5_get_calibration_extra_info
+ * (pod5/c++/pod5_format/c_api.h:315-350, 489-502), as flat arrays over every read of the file, all
+ * record batches in order.  The table (content type PGN_POD5_CONTENT_READS) is parsed on the first of
+ * these calls and kept on the handle.  Columns are found by name and their Arrow types checked:
+ *   read_id fixed_size_binary(16), signal list | large_list of uint64 (signal-table row indices),
+ *   num_samples uint64, calibration_offset / calibration_scale float32, read_number uint32,
+ *   channel uint16, well uint8 -- the flat columns of the current reads table (table version 3);
+ * dictionary columns and every other column are stepped over.
+ *   PGN_ERR_UNSUPPORTED  no reads table in the footer; one of these columns missing or of another type
+ *                        (older layouts keep the calibration in a dictionary struct) -- the column is
+ *                        named in pgn_pod5_file_error(); a null in a used column; body-compressed batches
+ *   PGN_ERR_CORRUPT      malformed Arrow, list offsets that do not rise, a listed row >= the signal
+ *                        table's rows
+ * Not covered: older reads-table layouts, the run-info table's contents (and the reads' dictionary
+ * columns that point into it), adapter trimming, writing a reads table from scratch. */
+int pgn_pod5_reads_info(const pgn_pod5_file *f, uint64_t *reads, uint32_t *batches, uint64_t *row_entries);
+/* Any pointer may be NULL.  read r lists signal rows rows[row_first[r] .. row_first[r + 1]);
+ * signal_samples[r] is the sum of those rows' `samples` (pod5_get_read_complete_sample_count): the
+ * read's length for the loader below.  num_samples is the column as stored, not cross-checked. */
+int pgn_pod5_reads_read(const pgn_pod5_file *f, uint8_t *read_ids /*16 x reads*/, uint64_t *row_first /*reads + 1*/,
+                        uint64_t *rows /*row_entries: signal-table row indices, read order*/,
+                        uint64_t *num_samples /*the column*/, uint64_t *signal_samples /*sum of the rows' `samples`*/,
+                        float *cal_offset, float *cal_scale, uint32_t *read_number, uint16_t *channel, uint8_t *well);
+
+/* ---- The loader: reads of a file -> HBM -----------------------------------------------------------
+ * pod5_get_read_complete_signal (c_api.h:489-502) and ReadRecord.signal / signal_pa (reader.py:356-368)
+ * for many reads at once, ending on the device: the host lists one chunk per signal row (its `samples`
+ * from the signal table), copies the rows' bytes from the file image into pinned staging (consecutive
+ * rows of one record batch in one copy: their bytes are adjacent in the column's data buffer), uploads
+ * them with the index arrays in one transfer and queues the decode on `stream`:
+ *   PGN_LOAD_ADC   int16 ADC counts              (pgn_decompress_reads_device_pa, PGN_OUT_INT16)
+ *   PGN_LOAD_PA    (adc + offset) * scale        (pgn_decompress_reads_device_pa, F32 or F16)
+ *   PGN_LOAD_NORM  the read normalised by itself (pgn_decompress_reads_device_norm, F32 or F16)
+ * The codec is the file's: VBZ for minknow.vbz, pgnano_variant for pgnano.signal.  An uncompressed
+ * table (large_list<int16>) is converted by a kernel of the loader with the same arithmetic.  The
+ * largest row is known on the host: when it is at most 262,144 samples the bounded decode runs, so the
+ * call never waits on the device.  Staging is kept on the context; a later call may wait for an
+ * earlier call's upload to finish, never for its kernels.  The output is ready in `stream` order.
+ * Read r of the call occupies d_out[offset_r .. + n_r) elements, n_r the sum of its rows' samples;
+ * offset_r is read_out_offsets[r], or the reads packed in call order.  Nothing is written outside it.
+ * Before any GPU call: a NULL or unknown argument, a read index >= the table's reads, a row index >=
+ * the signal table's rows or PGN_LOAD_NORM + F32 without d_adc is PGN_ERR_INVALID_ARG; a row above
+ * PGN_MAX_CHUNK_SAMPLES is PGN_ERR_UNSUPPORTED; max(offset_r + n_r) > out_capacity is
+ * PGN_ERR_DST_TOO_SMALL.  d_read_status[r] is the read's first chunk status that is not PGN_OK.
+ * Detail of a failure in pgn_pod5_last_error (pgnano_pod5.h). */
+typedef enum { PGN_LOAD_ADC = 0, PGN_LOAD_PA = 1, PGN_LOAD_NORM = 2 } pgn_load_kind;
+typedef struct pgn_pod5_load_args {
+    int32_t kind, out_type, pgnano_variant, pad;
+    const pgn_norm_params *norm;          /* PGN_LOAD_NORM */
+    void *d_out; uint64_t out_capacity;   /* elements of out_type */
+    const uint64_t *read_out_offsets;     /* host, nreads entries, or NULL = packed in call order */
+    int16_t *d_adc;                       /* as in the norm call (needed for NORM + F32) */
+    pgn_read_stats *d_stats;              /* optional, NORM */
+    int32_t *d_read_status;               /* optional */
+    uint64_t *read_offsets_out, *read_counts_out; /* host, optional: where each read went and its n */
+} pgn_pod5_load_args;
+/* core: the caller's own row lists and calibration (a file without a reads table works): read r is
+ * rows[row_first[r] .. row_first[r + 1]); cal_offset / cal_scale per read, needed for PGN_LOAD_PA only */
+int pgn_pod5_load_row_lists_device(pgn_ctx *ctx, const pgn_pod5_file *f, size_t nreads, const uint64_t *row_first,
+        const uint64_t *rows, const float *cal_offset, const float *cal_scale,
+        const pgn_pod5_load_args *args, void *stream);
+/* the file's reads read_index[0..nreads) (any order, repeats allowed; NULL = all reads in table order) */
+int pgn_pod5_load_reads_device(pgn_ctx *ctx, const pgn_pod5_file *f, const uint64_t *read_index, size_t nreads,
+        const pgn_pod5_load_args *args, void *stream);
 
 /* The row count of every signal record batch (counts: one entry per batch). */
 int pgn_pod5_signal_batch_row_counts(const pgn_pod5_file *f, uint64_t *counts);

@@ -24,8 +24,13 @@ from .codec import (
     vbz_compressed_signal_max_size,
     vbz_decompress_signal_capi,
 )
+from .pod5_file import LoadedReads, Pod5File, Pod5FileError, ReadsTable
 
 __all__ = [
+    "LoadedReads",
+    "Pod5File",
+    "Pod5FileError",
+    "ReadsTable",
     "EncodedBatch",
     "NativeLibraryError",
     "PGN_MAX_CHUNK_SAMPLES",

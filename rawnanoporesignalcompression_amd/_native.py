@@ -52,6 +52,19 @@ class ReadStats(C.Structure):
                 ("mad4", C.c_uint32), ("centre", C.c_float), ("spread", C.c_float)]
 
 
+# pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
+PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
+LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
+
+
+class LoadArgs(C.Structure):
+    """pgn_pod5_load_args"""
+    _fields_ = [("kind", C.c_int32), ("out_type", C.c_int32), ("pgnano_variant", C.c_int32), ("pad", C.c_int32),
+                ("norm", C.POINTER(NormParams)), ("d_out", C.c_void_p), ("out_capacity", C.c_uint64),
+                ("read_out_offsets", C.c_void_p), ("d_adc", C.c_void_p), ("d_stats", C.c_void_p),
+                ("d_read_status", C.c_void_p), ("read_offsets_out", C.c_void_p), ("read_counts_out", C.c_void_p)]
+
+
 # every symbol include/pgnano_hip.h declares: (name, restype, argtypes)
 _VP, _SZ, _U64P, _U32P, _I32P = C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p
 SIGNATURES = [
@@ -91,6 +104,10 @@ SIGNATURES = [
     ("pgn_decompress_reads_device_norm", C.c_int,
      [_VP, C.c_int, C.c_uint32, _SZ, _SZ, _U64P, _VP, _U64P, _U64P, _U32P, _VP, C.c_int, _U64P, _VP, _VP, _VP, _I32P,
       _VP]),
+    ("pgn_decompress_reads_device_pa", C.c_int,
+     [_VP, C.c_int, C.c_uint32, _SZ, _SZ, _U64P, _VP, _U64P, _U64P, _U32P, _VP, C.c_int, _U64P, _VP, _VP, _I32P, _I32P,
+      _VP]),
+    ("pgn_reads_status_device", C.c_int, [_VP, _SZ, _U64P, _I32P, _I32P, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),
@@ -135,6 +152,10 @@ SIGNATURES = [
     ("pgn_pod5_transcode_part", C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p), _VP]),
     ("pgn_pod5_part_get", C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("pgn_pod5_part_free", C.c_int, [_VP]),
+    ("pgn_pod5_reads_info", C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("pgn_pod5_reads_read", C.c_int, [_VP] * 11),
+    ("pgn_pod5_load_row_lists_device", C.c_int, [_VP, _VP, _SZ, _U64P, _U64P, _VP, _VP, C.POINTER(LoadArgs), _VP]),
+    ("pgn_pod5_load_reads_device", C.c_int, [_VP, _VP, _U64P, _SZ, C.POINTER(LoadArgs), _VP]),
 ]
 
 

@@ -476,6 +476,90 @@ class PGNanoCodec:
         caller.wait_stream(ls)
         return out, ro, ReadStats(raw), status
 
+    def decompress_reads_pa(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, cal_offset=None,
+                            cal_scale=None, *, dtype=None, out=None, read_out_offsets=None, max_chunk_samples: int = 0,
+                            stream: int | None = None):
+        """Decode whole reads straight to the calibrated signal, each read contiguous; returns
+        (out, read_out_offsets, read statuses, chunk statuses).
+
+        The reads-shaped :meth:`decompress_batch_pa` (pgn_decompress_reads_device_pa): the chunks are in read
+        order, ``read_first_chunk`` (nreads + 1 entries) says which are whose, and ``cal_offset`` /
+        ``cal_scale`` have one float32 entry per **read** (ignored, may be None, for ``dtype=torch.int16``,
+        which gives the reads' ADC counts).  dtype ``torch.float32`` (default), ``torch.float16`` or
+        ``torch.int16``: the values are :meth:`decompress_batch_pa`'s bit for bit.  out / read_out_offsets: the
+        destination (of ``dtype``) and each read's first element in it (default: packed).
+        max_chunk_samples: the caller's bound on the chunk sizes, 0 for none.  A read's status is its first
+        chunk status that is not 0, in chunk order (0 for a read without chunks)."""
+        import torch
+
+        dtype = torch.float32 if dtype is None else dtype
+        types = {torch.int16: _native.PGN_OUT_INT16, torch.float32: _native.PGN_OUT_F32,
+                 torch.float16: _native.PGN_OUT_F16}
+        if dtype not in types:
+            raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.int16 (got {dtype})")
+        if int(max_chunk_samples) < 0:
+            raise ValueError("max_chunk_samples must be >= 0 (0: no bound)")
+        _require_device(blobs, "blobs", self.device)
+        nchunks = int(sample_counts.numel())
+        nreads = int(read_first_chunk.numel()) - 1
+        if nreads < 0:
+            raise ValueError("read_first_chunk needs nreads + 1 entries")
+        if out is not None:
+            _require_device(out, "out", self.device)
+            if out.dtype != dtype:
+                raise ValueError(f"out must have dtype {dtype} (got {out.dtype})")
+        calibrated = dtype != torch.int16
+        if calibrated:
+            for t, name in ((cal_offset, "cal_offset"), (cal_scale, "cal_scale")):
+                if t is None or int(t.numel()) != nreads:
+                    raise ValueError(f"{name} must have one entry per read ({nreads})")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = blobs.device
+            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
+            first = read_first_chunk.to(device=dev, dtype=torch.int64).contiguous()
+            ends = torch.zeros(nchunks + 1, dtype=torch.int64, device=dev)
+            ends[1:] = torch.cumsum(counts.to(torch.int64), 0)
+            if read_out_offsets is None:
+                ro = ends[first[:-1]].contiguous()  # packed: a read starts where its first chunk would
+            else:
+                ro = read_out_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            if out is None:
+                out = torch.empty(max(int(ends[-1].item()), 1), dtype=dtype, device=dev)
+            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
+            co = cal_offset.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
+            cs = cal_scale.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
+            status = torch.full((nchunks,), -1, dtype=torch.int32, device=dev)
+            read_status = torch.full((nreads,), -1, dtype=torch.int32, device=dev)
+            _check(self._lib.pgn_decompress_reads_device_pa(
+                self._h, self._pa_codec, int(max_chunk_samples), nreads, nchunks, _ptr(first), _ptr(blobs), _ptr(bo),
+                _ptr(bs), _ptr(counts), _ptr(out), types[dtype], _ptr(ro), _ptr(co), _ptr(cs), _ptr(read_status),
+                _ptr(status), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return out, ro, read_status, status
+
+    def reads_status(self, read_first_chunk, chunk_status, stream: int | None = None):
+        """Each read's first chunk status that is not 0, in chunk order (pgn_reads_status_device): the
+        per-read statuses for :meth:`decompress_reads_norm`'s chunk statuses."""
+        import torch
+
+        _require_device(chunk_status, "chunk_status", self.device)
+        nreads = int(read_first_chunk.numel()) - 1
+        if nreads < 0:
+            raise ValueError("read_first_chunk needs nreads + 1 entries")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = chunk_status.device
+            first = read_first_chunk.to(device=dev, dtype=torch.int64).contiguous()
+            cs = chunk_status.to(dtype=torch.int32).contiguous()
+            out = torch.full((nreads,), -1, dtype=torch.int32, device=dev)
+            _check(self._lib.pgn_reads_status_device(self._h, nreads, _ptr(first), _ptr(cs), _ptr(out), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return out
+
     def synth_reads(self, nreads: int, samples_per_read, seed: int = 42, first_read: int = 0, read_stride: int = 1,
                     p_switch_q16: int = 6554, level_mean: int = 500, level_sd: int = 60, noise_sd: int = 12,
                     out=None):

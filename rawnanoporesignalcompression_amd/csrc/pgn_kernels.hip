@@ -2120,6 +2120,14 @@ struct pgn_ctx {
     uint64_t* normReadN = nullptr;
     pgn_read_stats* normStats = nullptr;
     size_t normChunks = 0, normReads = 0;
+    // pgn_decompress_reads_device_pa: the reads' calibration expanded to chunks (the chunks' output
+    // offsets share normChunkOut)
+    float* paChunkOffset = nullptr;
+    float* paChunkScale = nullptr;
+    size_t paChunks = 0;
+    // an object of another translation unit (the POD5 loader's staging, pgn_internal.h)
+    void* ext = nullptr;
+    void (*extDestroy)(void*) = nullptr;
     std::mutex mu;
     // combined per-chunk host calls (PcArena): pcOpen = the arena new calls join (-1: none idle)
     std::mutex pcMu;
@@ -2277,6 +2285,10 @@ int pgn_ctx_destroy(pgn_ctx* c)
     if (!c) return PGN_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    if (c->haveLast) (void)hipEventSynchronize(c->evLast);
+    if (c->ext && c->extDestroy) c->extDestroy(c->ext);
+    (void)hipFree(c->paChunkOffset);
+    (void)hipFree(c->paChunkScale);
     (void)hipFree(c->encScratch);
     (void)hipFree(c->epochs);
     (void)hipFree(c->decScratch);
@@ -3374,6 +3386,130 @@ extern "C" int pgn_decompress_reads_device_norm(pgn_ctx* c, int codec, uint32_t 
     rc = launch_read_stats(c, a, s);
     if (rc == PGN_OK && nchunks) {
         const sel::NormArgs na{adc, d_out, c->normChunkOut, d_sample_counts, c->normChunkRead, stats, nchunks};
+        const dim3 grid((unsigned)std::min<size_t>(nchunks, 1u << 20), sel::kNormSplit);
+        if (out_type == PGN_OUT_F32)
+            hipLaunchKernelGGL(sel::norm_convert_kernel<float>, grid, dim3(256), 0, s, na);
+        else
+            hipLaunchKernelGGL(sel::norm_convert_kernel<_Float16>, grid, dim3(256), 0, s, na);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return rc;
+}
+
+// ---- whole reads, calibrated (pgn_decompress_reads_device_pa) -----------------------------------
+static int ensure_reads_pa(pgn_ctx* c, size_t nchunks)
+{
+    int rc = ensure_norm(c, 0, nchunks);  // normChunkOut (and the norm call's other per-chunk array)
+    if (rc != PGN_OK) return rc;
+    if (nchunks > c->paChunks) {
+        wait_last_host(c);
+        (void)hipFree(c->paChunkOffset);
+        (void)hipFree(c->paChunkScale);
+        c->paChunkOffset = nullptr;
+        c->paChunkScale = nullptr;
+        c->paChunks = 0;
+        HIPCHK(hipMalloc(&c->paChunkOffset, nchunks * sizeof(float)));
+        HIPCHK(hipMalloc(&c->paChunkScale, nchunks * sizeof(float)));
+        c->paChunks = nchunks;
+    }
+    return PGN_OK;
+}
+
+static int launch_reads_status(size_t nreads, const uint64_t* d_first, const int32_t* d_chunk_status, int32_t* d_read_status,
+                               hipStream_t s)
+{
+    hipLaunchKernelGGL(sel::reads_status_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, s, (uint64_t)nreads,
+                       d_first, d_chunk_status, d_read_status);
+    HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+extern "C" int pgn_decompress_reads_device_pa(pgn_ctx* c, int codec, uint32_t max_chunk_samples, size_t nreads,
+                                              size_t nchunks, const uint64_t* d_read_first_chunk, const uint8_t* d_in,
+                                              const uint64_t* d_in_offsets, const uint64_t* d_in_sizes,
+                                              const uint32_t* d_sample_counts, void* d_out, int out_type,
+                                              const uint64_t* d_read_out_offsets, const float* d_read_cal_offset,
+                                              const float* d_read_cal_scale, int32_t* d_read_status,
+                                              int32_t* d_chunk_status, void* stream)
+{
+    if (!c) return PGN_ERR_INVALID_ARG;
+    const int k = bounded_codec(codec);
+    if (k < 0 || (out_type != PGN_OUT_INT16 && out_type != PGN_OUT_F32 && out_type != PGN_OUT_F16)) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;  // arrays of no entries may be NULL
+    if (!d_read_first_chunk || !d_out || !d_read_out_offsets) return PGN_ERR_INVALID_ARG;
+    if (nchunks && (!d_in || !d_in_offsets || !d_in_sizes || !d_sample_counts || !d_chunk_status)) return PGN_ERR_INVALID_ARG;
+    const bool cal = out_type != PGN_OUT_INT16;
+    if (cal && (!d_read_cal_offset || !d_read_cal_scale)) return PGN_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    int rc = PGN_OK;
+    if (nchunks) {
+        rc = ensure_reads_pa(c, nchunks);
+        if (rc != PGN_OK) return rc;
+        hipLaunchKernelGGL(sel::expand_reads_pa_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, s,
+                           (uint64_t)nreads, d_read_first_chunk, d_read_out_offsets, d_sample_counts,
+                           cal ? d_read_cal_offset : nullptr, cal ? d_read_cal_scale : nullptr, c->normChunkOut,
+                           c->paChunkOffset, c->paChunkScale);
+        HIPCHK(hipGetLastError());
+        // the decode of pgn_decompress_batch_device_pa, with the expanded arrays
+        const DecOut out(d_out, out_type, cal ? c->paChunkOffset : nullptr, cal ? c->paChunkScale : nullptr);
+        rc = launch_decode(c, k, nchunks, d_in, d_in_offsets, d_in_sizes, out, c->normChunkOut, d_sample_counts,
+                           d_chunk_status, s, max_chunk_samples);
+        if (rc != PGN_OK) return rc;
+    }
+    if (d_read_status) rc = launch_reads_status(nreads, d_read_first_chunk, d_chunk_status, d_read_status, s);
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return rc;
+}
+
+extern "C" int pgn_reads_status_device(pgn_ctx* c, size_t nreads, const uint64_t* d_read_first_chunk,
+                                       const int32_t* d_chunk_status, int32_t* d_read_status, void* stream)
+{
+    if (!c || !d_read_first_chunk || !d_read_status) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    const int rc = launch_reads_status(nreads, d_read_first_chunk, d_chunk_status, d_read_status, s);
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return rc;
+}
+
+// ---- in-library entry points of the POD5 loader (pgn_internal.h) --------------------------------
+void* pgn_ctx_ext_get(pgn_ctx* c) { return c ? c->ext : nullptr; }
+void pgn_ctx_ext_set(pgn_ctx* c, void* p, void (*destroy)(void*))
+{
+    c->ext = p;
+    c->extDestroy = destroy;
+}
+int pgn_ctx_device(pgn_ctx* c) { return c->device; }
+bool pgn_norm_params_valid(const pgn_norm_params* params) { return sel::params_valid(params); }
+
+int pgn_norm_decoded_reads(pgn_ctx* c, size_t nreads, size_t nchunks, const int16_t* d_adc, void* d_out, int out_type,
+                           const uint64_t* d_read_out_offsets, const uint64_t* d_read_n, const uint64_t* d_chunk_out,
+                           const uint32_t* d_sample_counts, const uint32_t* d_chunk_read, const pgn_norm_params* params,
+                           pgn_read_stats* d_stats, void* stream)
+{
+    if (!c || !sel::params_valid(params) || (out_type != PGN_OUT_F32 && out_type != PGN_OUT_F16)) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    int rc = ensure_norm(c, nreads, 0);
+    if (rc != PGN_OK) return rc;
+    pgn_read_stats* stats = d_stats ? d_stats : c->normStats;
+    const sel::StatsArgs a{d_adc, d_read_out_offsets, d_read_n, nreads, *params, stats, nullptr, nullptr};
+    rc = launch_read_stats(c, a, s);
+    if (rc == PGN_OK && nchunks) {
+        const sel::NormArgs na{d_adc, d_out, d_chunk_out, d_sample_counts, d_chunk_read, stats, nchunks};
         const dim3 grid((unsigned)std::min<size_t>(nchunks, 1u << 20), sel::kNormSplit);
         if (out_type == PGN_OUT_F32)
             hipLaunchKernelGGL(sel::norm_convert_kernel<float>, grid, dim3(256), 0, s, na);

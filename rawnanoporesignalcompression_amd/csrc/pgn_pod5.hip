@@ -950,3 +950,395 @@ int pgn_pod5_part_free(pgn_pod5_part* part)
 }  // extern "C"
 
 
+
+// ---------------------------------------------------------------------------------------------
+// The loader: reads of an open POD5 file -> HBM (pgn_pod5_load_row_lists_device,
+// pgn_pod5_load_reads_device; include/pgnano_pod5file.h).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// the arithmetic of the decode's sample sink (pgn_c5.h sink_samples16): the int16 converted exactly, one
+// binary32 add, one binary32 multiply (an add feeding a multiply cannot contract to an FMA)
+__device__ __forceinline__ float raw_pa(uint32_t x16, float off, float scale)
+{
+    return ((float)(int32_t)(int16_t)(uint16_t)x16 + off) * scale;
+}
+// binary32 -> binary16 bits, round to nearest even, of the rounded product: the empty asm keeps the
+// compiler from fusing multiply and conversion into one rounding (v_fma_mixlo_f16)
+__device__ __forceinline__ uint32_t raw_f16_bits(float f)
+{
+    asm("" : "+v"(f));
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+}
+
+struct RawArgs {
+    const uint8_t* bytes;       // the uploaded rows: little-endian int16, each on a 2-byte boundary
+    const uint64_t* inOff;      // per chunk: byte offset of its first sample (even)
+    const uint64_t* chunkOut;   // per chunk: first element in out
+    const uint32_t* counts;     // per chunk: samples
+    const uint32_t* chunkRead;  // per chunk: its read
+    const float* calOffset;     // per read (unused for int16_t)
+    const float* calScale;
+    void* out;
+    uint64_t nchunks;
+};
+
+constexpr uint32_t kRawSplit = 8;  // workgroups that share one chunk (blockIdx.y)
+
+// Rows of an uncompressed signal table -> int16 / pA binary32 / pA binary16 at the read's place.  One
+// chunk per blockIdx.x step, its 16-byte vectors dealt to kRawSplit workgroups: a thread loads eight
+// samples with one 16-byte load from the 16-byte-aligned body of the row and stores them with 16-byte
+// stores when the destination is aligned too, else element by element; the up to seven samples before
+// the body and after its last whole vector go one per thread.  Reads in[0, n), writes out[0, n).
+template <class T>
+__global__ __launch_bounds__(256) void raw_convert_kernel(RawArgs a)
+{
+    for (uint64_t c = blockIdx.x; c < a.nchunks; c += gridDim.x) {
+        const uint32_t n = a.counts[c];
+        if (!n) continue;
+        float off = 0.0f, scale = 0.0f;
+        if constexpr (!__is_same(T, int16_t)) {
+            off = a.calOffset[a.chunkRead[c]];
+            scale = a.calScale[a.chunkRead[c]];
+        }
+        const uint16_t* in = reinterpret_cast<const uint16_t*>(a.bytes + a.inOff[c]);
+        T* out = reinterpret_cast<T*>(a.out) + a.chunkOut[c];
+        auto one = [&](uint32_t i) {
+            if constexpr (__is_same(T, int16_t)) reinterpret_cast<uint16_t*>(out)[i] = in[i];
+            else if constexpr (sizeof(T) == 4) out[i] = raw_pa(in[i], off, scale);
+            else reinterpret_cast<uint16_t*>(out)[i] = (uint16_t)raw_f16_bits(raw_pa(in[i], off, scale));
+        };
+        uint32_t head = (uint32_t)((16u - (uint32_t)((uintptr_t)in & 15u)) & 15u) >> 1;
+        if (head > n) head = n;
+        const uint32_t nvec = (n - head) >> 3;
+        const bool aligned = ((uintptr_t)(out + head) & 15u) == 0;
+        if (blockIdx.y == 0) {
+            if (threadIdx.x < head) one(threadIdx.x);
+            const uint32_t t = head + (nvec << 3) + threadIdx.x;
+            if (t < n) one(t);
+        }
+        const uint4* q = reinterpret_cast<const uint4*>(in + head);
+        for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < nvec; i += kRawSplit * 256) {
+            const uint4 v = q[i];
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            T* o = out + head + (size_t)i * 8;
+            if constexpr (__is_same(T, int16_t)) {
+                if (aligned) {
+                    *reinterpret_cast<uint4*>(o) = v;
+                } else {
+                    uint16_t* o16 = reinterpret_cast<uint16_t*>(o);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        o16[2 * j] = (uint16_t)w[j];
+                        o16[2 * j + 1] = (uint16_t)(w[j] >> 16);
+                    }
+                }
+            } else {
+                float f[8];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    f[2 * j] = raw_pa(w[j] & 0xFFFFu, off, scale);
+                    f[2 * j + 1] = raw_pa(w[j] >> 16, off, scale);
+                }
+                if constexpr (sizeof(T) == 4) {
+                    if (aligned) {
+                        reinterpret_cast<float4*>(o)[0] = make_float4(f[0], f[1], f[2], f[3]);
+                        reinterpret_cast<float4*>(o)[1] = make_float4(f[4], f[5], f[6], f[7]);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) o[j] = f[j];
+                    }
+                } else {
+                    uint32_t h[4];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) h[j] = raw_f16_bits(f[2 * j]) | (raw_f16_bits(f[2 * j + 1]) << 16);
+                    if (aligned) {
+                        *reinterpret_cast<uint4*>(o) = make_uint4(h[0], h[1], h[2], h[3]);
+                    } else {
+                        uint16_t* o16 = reinterpret_cast<uint16_t*>(o);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            o16[2 * j] = (uint16_t)h[j];
+                            o16[2 * j + 1] = (uint16_t)(h[j] >> 16);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The loader's staging, kept on the context (pgn_ctx_ext_*): one pinned block and its device copy.
+// evUp: the last upload has left the pinned block (the next call's host writes wait for it);
+// evDone: the last call's kernels have finished with the device block (the next upload waits for it
+// on the device, in stream order -- the host does not).
+struct LoadState {
+    std::mutex mu;
+    PinBuf h;
+    DevBuf d;
+    hipEvent_t evUp = nullptr, evDone = nullptr;
+    bool haveUp = false, haveDone = false;
+    CopyPool* pool = nullptr;
+};
+
+void load_state_destroy(void* p)
+{
+    LoadState* st = (LoadState*)p;
+    if (st->haveDone) (void)hipEventSynchronize(st->evDone);
+    if (st->h.p) (void)hipHostFree(st->h.p);
+    if (st->d.p) (void)hipFree(st->d.p);
+    if (st->evUp) (void)hipEventDestroy(st->evUp);
+    if (st->evDone) (void)hipEventDestroy(st->evDone);
+    delete st->pool;
+    delete st;
+}
+
+std::mutex g_loadStateMu;
+
+int load_state_of(pgn_ctx* ctx, LoadState*& out)
+{
+    std::lock_guard<std::mutex> g(g_loadStateMu);
+    LoadState* st = (LoadState*)pgn_ctx_ext_get(ctx);
+    if (!st) {
+        std::unique_ptr<LoadState> n(new LoadState());
+        P5CHK(hipEventCreateWithFlags(&n->evUp, hipEventDisableTiming));
+        P5CHK(hipEventCreateWithFlags(&n->evDone, hipEventDisableTiming));
+        n->pool = new CopyPool(host_threads());
+        st = n.release();
+        pgn_ctx_ext_set(ctx, st, load_state_destroy);
+    }
+    out = st;
+    return PGN_OK;
+}
+
+int load_fail(int rc, const char* fmt, unsigned long long a = 0, unsigned long long b = 0)
+{
+    snprintf(g_pod5_err, sizeof(g_pod5_err), fmt, a, b);
+    return rc;
+}
+
+int load_row_lists(pgn_ctx* ctx, const pgn_pod5_file* f, size_t nreads, const uint64_t* row_first, const uint64_t* rows,
+                   const float* cal_offset, const float* cal_scale, const pgn_pod5_load_args* args, void* stream)
+{
+    // ---- arguments, before any GPU call
+    if (!ctx || !f || !args) return load_fail(PGN_ERR_INVALID_ARG, "NULL ctx, file or args");
+    const int kind = args->kind;
+    if (kind != PGN_LOAD_ADC && kind != PGN_LOAD_PA && kind != PGN_LOAD_NORM) return load_fail(PGN_ERR_INVALID_ARG, "unknown kind");
+    const int outType = args->out_type;
+    if (kind == PGN_LOAD_ADC ? outType != PGN_OUT_INT16 : (outType != PGN_OUT_F32 && outType != PGN_OUT_F16))
+        return load_fail(PGN_ERR_INVALID_ARG, "out_type does not fit the kind");
+    uint64_t tableRows = 0;
+    int sigType = 0;
+    pgn_pod5_signal_info(f, &tableRows, nullptr, &sigType, nullptr, nullptr);
+    const bool raw = sigType == PGN_POD5_SIGNAL_UNCOMPRESSED;
+    if (sigType == PGN_POD5_SIGNAL_PGNANO && (args->pgnano_variant < PGN_VARIANT_C5 || args->pgnano_variant > PGN_VARIANT_VBZ0))
+        return load_fail(PGN_ERR_INVALID_ARG, "unknown pgnano_variant");
+    const int codec = sigType == PGN_POD5_SIGNAL_VBZ ? PGN_POD5_CODEC_VBZ : args->pgnano_variant;
+    if (kind == PGN_LOAD_NORM && !pgn_norm_params_valid(args->norm)) return load_fail(PGN_ERR_INVALID_ARG, "norm parameters");
+    if (nreads == 0) return PGN_OK;
+    if (!row_first || !args->d_out) return load_fail(PGN_ERR_INVALID_ARG, "NULL row_first or d_out");
+    if (kind == PGN_LOAD_PA && (!cal_offset || !cal_scale)) return load_fail(PGN_ERR_INVALID_ARG, "PGN_LOAD_PA without calibration");
+    if (kind == PGN_LOAD_NORM && outType == PGN_OUT_F32 && !args->d_adc)
+        return load_fail(PGN_ERR_INVALID_ARG, "PGN_LOAD_NORM as float32 needs d_adc");
+    if (nreads > 0xFFFFFFFFull) return load_fail(PGN_ERR_INVALID_ARG, "more than 2^32 - 1 reads");
+    for (size_t r = 0; r < nreads; r++)
+        if (row_first[r + 1] < row_first[r]) return load_fail(PGN_ERR_INVALID_ARG, "row_first does not rise at read %llu", r);
+    const size_t nchunks = (size_t)(row_first[nreads] - row_first[0]);
+    if (nchunks && !rows) return load_fail(PGN_ERR_INVALID_ARG, "NULL rows");
+    const uint64_t* rw = rows + (nchunks ? row_first[0] : 0);
+    std::vector<const uint8_t*> src(nchunks);
+    std::vector<uint64_t> nbytes(nchunks);
+    std::vector<uint32_t> cnt(nchunks);
+    if (pgn_pod5_signal_row_spans(f, nchunks, rw, src.data(), nbytes.data(), cnt.data()) != PGN_OK)
+        return load_fail(PGN_ERR_INVALID_ARG, "a row index is at or beyond the signal table's %llu rows", tableRows);
+    uint32_t maxRow = 0;
+    uint64_t dataBytes = 0;
+    for (size_t i = 0; i < nchunks; i++) {
+        if (cnt[i] > PGN_MAX_CHUNK_SAMPLES)
+            return load_fail(PGN_ERR_UNSUPPORTED, "row %llu: %llu samples above PGN_MAX_CHUNK_SAMPLES", rw[i], cnt[i]);
+        if (raw && nbytes[i] != 2ull * cnt[i]) return load_fail(PGN_ERR_CORRUPT, "row %llu: list length differs from `samples`", rw[i]);
+        maxRow = cnt[i] > maxRow ? cnt[i] : maxRow;
+        dataBytes += nbytes[i];
+    }
+    // ---- the layout: where each read goes, and that it fits
+    // staging, 64-bit arrays first: first chunk (nreads + 1) | read offset | read n | chunk byte offset |
+    // chunk bytes | chunk output offset; then float32 offset | scale per read; uint32 count | read per chunk
+    const size_t o64 = 0, n64 = (nreads + 1) + 2 * nreads + 3 * nchunks;
+    const size_t oF = o64 + 8 * n64, oU = oF + 8 * nreads, oData = up256(oU + 8 * nchunks);
+    const size_t upBytes = oData + (size_t)dataBytes;
+    const size_t oStatus = up256(upBytes), devBytes = oStatus + up256(4 * nchunks + 4);
+    std::vector<uint64_t> readOff(nreads), readN(nreads);
+    uint64_t packed = 0;
+    for (size_t r = 0; r < nreads; r++) {
+        uint64_t n = 0;
+        for (uint64_t k = row_first[r] - row_first[0]; k < row_first[r + 1] - row_first[0]; k++) n += cnt[k];
+        readN[r] = n;
+        readOff[r] = args->read_out_offsets ? args->read_out_offsets[r] : packed;
+        packed += n;
+        if (readOff[r] > args->out_capacity || n > args->out_capacity - readOff[r])
+            return load_fail(PGN_ERR_DST_TOO_SMALL, "read %llu does not fit out_capacity %llu", r, args->out_capacity);
+    }
+    for (size_t r = 0; r < nreads; r++) {
+        if (args->read_offsets_out) args->read_offsets_out[r] = readOff[r];
+        if (args->read_counts_out) args->read_counts_out[r] = readN[r];
+    }
+    // ---- staging
+    LoadState* st = nullptr;
+    P5CHK(hipSetDevice(pgn_ctx_device(ctx)));
+    int rc = load_state_of(ctx, st);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> g(st->mu);
+    if (st->haveUp) P5CHK(hipEventSynchronize(st->evUp));  // the pinned block is free again
+    rc = ensure_pin(st->h, upBytes);
+    if (rc) return rc;
+    if (devBytes > st->d.cap && st->haveDone) P5CHK(hipEventSynchronize(st->evDone));  // growth only
+    rc = ensure_devbuf(st->d, devBytes);
+    if (rc) return rc;
+    uint8_t* h = st->h.p;
+    uint64_t* hFirst = (uint64_t*)(h + o64);
+    uint64_t *hReadOff = hFirst + nreads + 1, *hReadN = hReadOff + nreads, *hInOff = hReadN + nreads, *hInSz = hInOff + nchunks,
+             *hChunkOut = hInSz + nchunks;
+    float *hCalOff = (float*)(h + oF), *hCalScale = hCalOff + nreads;
+    uint32_t *hCnt = (uint32_t*)(h + oU), *hChunkRead = hCnt + nchunks;
+    std::vector<CopyJob> jobs;
+    uint64_t at = 0;
+    for (size_t r = 0; r < nreads; r++) {
+        hFirst[r] = row_first[r] - row_first[0];
+        hReadOff[r] = readOff[r];
+        hReadN[r] = readN[r];
+        hCalOff[r] = cal_offset ? cal_offset[r] : 0.0f;
+        hCalScale[r] = cal_scale ? cal_scale[r] : 1.0f;
+        uint64_t acc = 0;
+        for (uint64_t k = hFirst[r]; k < row_first[r + 1] - row_first[0]; k++) {
+            hInOff[k] = at;
+            hInSz[k] = nbytes[k];
+            hChunkOut[k] = readOff[r] + acc;
+            hCnt[k] = cnt[k];
+            hChunkRead[k] = (uint32_t)r;
+            // consecutive rows of one record batch are adjacent in the file: one copy
+            if (nbytes[k]) {
+                if (!jobs.empty() && jobs.back().src + jobs.back().n == src[k]) jobs.back().n += (size_t)nbytes[k];
+                else jobs.push_back({h + oData + at, src[k], (size_t)nbytes[k]});
+            }
+            at += nbytes[k];
+            acc += cnt[k];
+        }
+    }
+    hFirst[nreads] = nchunks;
+    st->pool->run(jobs.data(), jobs.size());
+    // ---- device: one upload, then the decode
+    const hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t)pgn_ctx_stream(ctx);
+    if (st->haveDone) P5CHK(hipStreamWaitEvent(s, st->evDone, 0));
+    uint8_t* d = st->d.p;
+    P5CHK(hipMemcpyAsync(d, h, upBytes, hipMemcpyHostToDevice, s));
+    P5CHK(hipEventRecord(st->evUp, s));
+    st->haveUp = true;
+    const uint64_t* dFirst = (const uint64_t*)(d + o64);
+    const uint64_t *dReadOff = dFirst + nreads + 1, *dReadN = dReadOff + nreads, *dInOff = dReadN + nreads,
+                   *dInSz = dInOff + nchunks, *dChunkOut = dInSz + nchunks;
+    const float *dCalOff = (const float*)(d + oF), *dCalScale = dCalOff + nreads;
+    const uint32_t *dCnt = (const uint32_t*)(d + oU), *dChunkRead = dCnt + nchunks;
+    int32_t* dChunkStatus = (int32_t*)(d + oStatus);
+    // the largest row is known here: a bound at or below the batched passes' chunk size needs no scan
+    const uint32_t bound = maxRow <= 262144u ? (maxRow ? maxRow : 1u) : 0u;
+    if (!raw) {
+        if (kind == PGN_LOAD_NORM) {
+            rc = pgn_decompress_reads_device_norm(ctx, codec, bound, nreads, nchunks, dFirst, d + oData, dInOff, dInSz, dCnt,
+                                                  args->d_out, outType, dReadOff, args->d_adc, args->norm, args->d_stats,
+                                                  dChunkStatus, s);
+            if (rc == PGN_OK && args->d_read_status)
+                rc = pgn_reads_status_device(ctx, nreads, dFirst, dChunkStatus, args->d_read_status, s);
+        } else {
+            rc = pgn_decompress_reads_device_pa(ctx, codec, bound, nreads, nchunks, dFirst, d + oData, dInOff, dInSz, dCnt,
+                                                args->d_out, outType, dReadOff, dCalOff, dCalScale, args->d_read_status,
+                                                dChunkStatus, s);
+        }
+        if (rc == PGN_ERR_HIP) snprintf(g_pod5_err, sizeof(g_pod5_err), "%s", pgn_last_error());
+    } else {
+        int16_t* adc = args->d_adc ? args->d_adc : (int16_t*)args->d_out;
+        RawArgs ra{d + oData, dInOff, dChunkOut, dCnt, dChunkRead, dCalOff, dCalScale, args->d_out, nchunks};
+        const dim3 grid((unsigned)std::min<size_t>(nchunks, 1u << 20), kRawSplit);
+        if (nchunks) {
+            if (kind == PGN_LOAD_NORM) ra.out = adc;
+            if (kind != PGN_LOAD_PA)
+                hipLaunchKernelGGL(raw_convert_kernel<int16_t>, grid, dim3(256), 0, s, ra);
+            else if (outType == PGN_OUT_F32)
+                hipLaunchKernelGGL(raw_convert_kernel<float>, grid, dim3(256), 0, s, ra);
+            else
+                hipLaunchKernelGGL(raw_convert_kernel<_Float16>, grid, dim3(256), 0, s, ra);
+            P5CHK(hipGetLastError());
+        }
+        if (kind == PGN_LOAD_NORM)
+            rc = pgn_norm_decoded_reads(ctx, nreads, nchunks, adc, args->d_out, outType, dReadOff, dReadN, dChunkOut, dCnt,
+                                        dChunkRead, args->norm, args->d_stats, s);
+        if (rc == PGN_OK && args->d_read_status) P5CHK(hipMemsetAsync(args->d_read_status, 0, 4 * nreads, s));
+    }
+    P5CHK(hipEventRecord(st->evDone, s));
+    st->haveDone = true;
+    return rc;
+}
+
+int load_reads(pgn_ctx* ctx, const pgn_pod5_file* f, const uint64_t* read_index, size_t nreads, const pgn_pod5_load_args* args,
+               void* stream)
+{
+    if (!ctx || !f || !args) return load_fail(PGN_ERR_INVALID_ARG, "NULL ctx, file or args");
+    uint64_t reads = 0, entries = 0;
+    int rc = pgn_pod5_reads_info(f, &reads, nullptr, &entries);
+    if (rc) {
+        snprintf(g_pod5_err, sizeof(g_pod5_err), "%s", pgn_pod5_file_error());
+        return rc;
+    }
+    if (!read_index) nreads = (size_t)reads;
+    for (size_t i = 0; read_index && i < nreads; i++)
+        if (read_index[i] >= reads)
+            return load_fail(PGN_ERR_INVALID_ARG, "read index %llu is at or beyond the table's %llu reads", read_index[i], reads);
+    std::vector<uint64_t> first(reads + 1), rows(entries);
+    std::vector<float> off(reads), scale(reads);
+    pgn_pod5_reads_read(f, nullptr, first.data(), rows.data(), nullptr, nullptr, off.data(), scale.data(), nullptr, nullptr,
+                        nullptr);
+    if (!read_index)
+        return load_row_lists(ctx, f, nreads, first.data(), rows.data(), off.data(), scale.data(), args, stream);
+    std::vector<uint64_t> selFirst(nreads + 1, 0), selRows;
+    std::vector<float> selOff(nreads), selScale(nreads);
+    for (size_t i = 0; i < nreads; i++) {
+        const uint64_t r = read_index[i];
+        selRows.insert(selRows.end(), rows.begin() + first[r], rows.begin() + first[r + 1]);
+        selFirst[i + 1] = selRows.size();
+        selOff[i] = off[r];
+        selScale[i] = scale[r];
+    }
+    return load_row_lists(ctx, f, nreads, selFirst.data(), selRows.data(), selOff.data(), selScale.data(), args, stream);
+}
+
+template <class F>
+int load_guarded(F&& fn)
+{
+    try {
+        return fn();
+    } catch (const std::bad_alloc&) {
+        snprintf(g_pod5_err, sizeof(g_pod5_err), "out of host memory");
+        return PGN_ERR_IO;
+    } catch (const std::exception& e) {
+        snprintf(g_pod5_err, sizeof(g_pod5_err), "%s", e.what());
+        return PGN_ERR_CORRUPT;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgn_pod5_load_row_lists_device(pgn_ctx* ctx, const pgn_pod5_file* f, size_t nreads, const uint64_t* row_first,
+                                   const uint64_t* rows, const float* cal_offset, const float* cal_scale,
+                                   const pgn_pod5_load_args* args, void* stream)
+{
+    return load_guarded([&] { return load_row_lists(ctx, f, nreads, row_first, rows, cal_offset, cal_scale, args, stream); });
+}
+
+int pgn_pod5_load_reads_device(pgn_ctx* ctx, const pgn_pod5_file* f, const uint64_t* read_index, size_t nreads,
+                               const pgn_pod5_load_args* args, void* stream)
+{
+    return load_guarded([&] { return load_reads(ctx, f, read_index, nreads, args, stream); });
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <mutex>
 #include <random>
 #include <stdexcept>
 #include <string>
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "../../include/pgnano_pod5file.h"
+#include "pgn_internal.h"
 
 namespace {
 
@@ -414,6 +416,19 @@ struct SignalBatch {
     uint64_t data_len;            // bytes addressable from `data`
 };
 
+// the reads table, parsed on the first pgn_pod5_reads_* call and kept (status and message included)
+struct ReadsCache {
+    int status = PGN_OK;
+    std::string err;
+    uint32_t batches = 0;
+    std::vector<uint8_t> ids, well;           // 16 x reads; reads
+    std::vector<uint64_t> rowFirst, rows;     // reads + 1; signal-table row indices in read order
+    std::vector<uint64_t> numSamples, signalSamples;
+    std::vector<float> calOffset, calScale;
+    std::vector<uint32_t> readNumber;
+    std::vector<uint16_t> channel;
+};
+
 }  // namespace
 
 struct pgn_pod5_file {
@@ -429,7 +444,11 @@ struct pgn_pod5_file {
     int signal_type = PGN_POD5_SIGNAL_UNCOMPRESSED;
     std::vector<KV> schema_metadata, footer_metadata;
     std::vector<SignalBatch> batches;
+    std::vector<uint64_t> batchFirst;  // first table row of every batch, then the row count
     uint64_t rows = 0, data_bytes = 0, total_samples = 0;
+    // reads table (lazy; the handle is const to its readers)
+    mutable std::mutex readsMu;
+    mutable std::unique_ptr<ReadsCache> reads;
 };
 
 namespace {
@@ -616,6 +635,12 @@ void parse_file(pgn_pod5_file& f)
     if (f.signal_index < 0) corrupt("no signal table in the footer");
     const auto& s = f.embedded[f.signal_index];
     parse_signal_table(f, (size_t)s.offset, (size_t)s.length);
+    uint64_t row = 0;
+    for (const SignalBatch& b : f.batches) {
+        f.batchFirst.push_back(row);
+        row += b.rows;
+    }
+    f.batchFirst.push_back(row);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1061,6 +1086,177 @@ void read_signal_lists(const IpcReader& r, const Block& blk, int iSignal, std::v
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The reads table as flat arrays (pgn_pod5_reads_*): what the reference's reader gives through
+// pod5_get_read_batch_row_info_data, pod5_get_signal_row_indices and
+// pod5_get_read_complete_sample_count (c_api.h:315-350, 489-502).  Columns are found by name and
+// their types checked; every other column is stepped over by its buffer count.
+struct ReadsColumn {
+    const char* name;
+    uint8_t type;
+    int32_t bits;     // Int width, FixedSizeBinary width, or 32 for a binary32 FloatingPoint
+    bool isSigned;
+    int width;        // bytes per row
+};
+const ReadsColumn kReadsColumns[] = {
+    {"read_id", AT_FixedSizeBinary, 16, false, 16}, {"num_samples", AT_Int, 64, false, 8},
+    {"calibration_offset", AT_FloatingPoint, 32, false, 4}, {"calibration_scale", AT_FloatingPoint, 32, false, 4},
+    {"read_number", AT_Int, 32, false, 4}, {"channel", AT_Int, 16, false, 2}, {"well", AT_Int, 8, false, 1}};
+constexpr int kReadsFlat = (int)(sizeof(kReadsColumns) / sizeof(kReadsColumns[0]));
+
+bool reads_column_matches(const ArrowField& f, const ReadsColumn& c)
+{
+    if (f.dictionary || f.type != c.type) return false;
+    switch (c.type) {
+    case AT_FixedSizeBinary: return f.byte_width == c.bits;
+    case AT_FloatingPoint: return f.fp_precision == 1;
+    default: return f.int_bits == c.bits && f.int_signed == c.isSigned;
+    }
+}
+
+void parse_reads_table(const pgn_pod5_file& f, ReadsCache& out)
+{
+    const pgn_pod5_file::Embedded* em = nullptr;
+    for (const auto& e : f.embedded)
+        if (e.content_type == PGN_POD5_CONTENT_READS) {
+            em = &e;
+            break;
+        }
+    if (!em) unsupported("no reads table in the footer");
+    const IpcReader r(f.raw.data() + em->offset, (size_t)em->length);
+    int col[kReadsFlat], iSignal = -1;
+    for (int k = 0; k < kReadsFlat; k++) col[k] = -1;
+    for (size_t i = 0; i < r.fields.size(); i++) {
+        for (int k = 0; k < kReadsFlat; k++)
+            if (r.fields[i].name == kReadsColumns[k].name) col[k] = (int)i;
+        if (r.fields[i].name == "signal") iSignal = (int)i;
+    }
+    for (int k = 0; k < kReadsFlat; k++) {
+        if (col[k] < 0)
+            unsupported(std::string("reads table: no flat column '") + kReadsColumns[k].name +
+                        "' (an older reads-table layout)");
+        if (!reads_column_matches(r.fields[col[k]], kReadsColumns[k]))
+            unsupported(std::string("reads table: column '") + kReadsColumns[k].name + "' has another type");
+    }
+    if (iSignal < 0) unsupported("reads table: no column 'signal'");
+    {
+        const ArrowField& s = r.fields[iSignal];
+        if (s.dictionary || (s.type != AT_List && s.type != AT_LargeList) || s.children.size() != 1 ||
+            s.children[0].dictionary || s.children[0].type != AT_Int || s.children[0].int_bits != 64 ||
+            s.children[0].int_signed)
+            unsupported("reads table: column 'signal' is not a list of uint64");
+    }
+    // every signal row's sample count, for the reads' complete sample counts
+    std::vector<uint32_t> rowSamples;
+    rowSamples.reserve(f.rows);
+    for (const SignalBatch& b : f.batches)
+        for (uint64_t i = 0; i < b.rows; i++) {
+            uint32_t s;
+            memcpy(&s, (const uint8_t*)b.samples + 4 * i, 4);
+            rowSamples.push_back(s);
+        }
+    out.batches = r.batches.len;
+    out.rowFirst.assign(1, 0);
+    for (uint32_t b = 0; b < r.batches.len; b++) {
+        IpcBatchIn in = r.batch(r.block(r.batches, b));
+        const int64_t length = fb_scalar<int64_t>(fb_subtable(fb_root(in.meta), 2), 0, 0);
+        // 16 bytes of read id per read: a larger length cannot fit the body (no product below overflows)
+        if (length < 0 || length > in.bodyLen / 16) corrupt("reads table: batch length out of range");
+        const size_t at = out.numSamples.size(), n = (size_t)length;
+        out.ids.resize(16 * (at + n));
+        out.numSamples.resize(at + n);
+        out.calOffset.resize(at + n);
+        out.calScale.resize(at + n);
+        out.readNumber.resize(at + n);
+        out.channel.resize(at + n);
+        out.well.resize(at + n);
+        void* const dst[kReadsFlat] = {out.ids.data() + 16 * at, out.numSamples.data() + at, out.calOffset.data() + at,
+                                       out.calScale.data() + at, out.readNumber.data() + at, out.channel.data() + at,
+                                       out.well.data() + at};
+        for (int c = 0; c < (int)r.fields.size(); c++) {
+            int flat = -1;
+            for (int k = 0; k < kReadsFlat; k++)
+                if (col[k] == c) flat = k;
+            if (flat < 0 && c != iSignal) {
+                size_t nodes = 0, buffers = 0;
+                count_layout(r.fields[c], nodes, buffers);
+                if (nodes > in.nNodes - in.ni || buffers > in.nBufs - in.bi)
+                    corrupt("Arrow record batch layout does not match the schema");
+                in.ni += (uint32_t)nodes;
+                in.bi += (uint32_t)buffers;
+                continue;
+            }
+            const char* name = flat >= 0 ? kReadsColumns[flat].name : "signal";
+            const auto nd = in.node();
+            if (nd.first != length) corrupt(std::string("reads table: length of column '") + name + "' differs from the batch");
+            if (nd.second != 0) unsupported(std::string("reads table: null entries in column '") + name + "'");
+            (void)in.buf();  // validity
+            if (flat >= 0) {
+                const auto vals = in.buf();
+                const int64_t w = kReadsColumns[flat].width;
+                if (vals.second < length * w) corrupt(std::string("reads table: values of column '") + name + "' too short");
+                if (n) memcpy(dst[flat], vals.first, n * (size_t)w);
+                continue;
+            }
+            const bool large = r.fields[c].type == AT_LargeList;
+            const auto ob = in.buf();
+            if (ob.second < (length + 1) * (large ? 8 : 4)) corrupt("reads table: signal offsets too short");
+            const auto cn = in.node();
+            if (cn.second != 0) unsupported("reads table: null entries in column 'signal'");
+            (void)in.buf();  // child validity
+            const auto vb = in.buf();
+            auto off = [&](int64_t i) -> int64_t {
+                if (large) return ld_i64(ob.first + 8 * i);
+                int32_t v;
+                memcpy(&v, ob.first + 4 * i, 4);
+                return v;
+            };
+            for (int64_t i = 0; i < length; i++) {
+                const int64_t a0 = off(i), a1 = off(i + 1);
+                if (a0 < 0 || a1 < a0 || a1 > vb.second / 8 || a1 > cn.first)
+                    corrupt("reads table: signal offsets not monotonic or beyond the values");
+                uint64_t total = 0;
+                for (int64_t k = a0; k < a1; k++) {
+                    const uint64_t row = (uint64_t)ld_i64(vb.first + 8 * k);
+                    if (row >= f.rows) corrupt("reads table lists a signal row beyond the table");
+                    out.rows.push_back(row);
+                    total += rowSamples[row];
+                }
+                out.signalSamples.push_back(total);
+                out.rowFirst.push_back(out.rows.size());
+            }
+        }
+        if (in.ni != in.nNodes || in.bi != in.nBufs) corrupt("Arrow record batch layout does not match the schema");
+    }
+}
+
+// The parsed reads table of f (parsed once; a failure is kept and reported again).
+const ReadsCache& reads_of(const pgn_pod5_file& f)
+{
+    std::lock_guard<std::mutex> g(f.readsMu);
+    if (!f.reads) {
+        std::unique_ptr<ReadsCache> rc(new ReadsCache());
+        try {
+            parse_reads_table(f, *rc);
+        } catch (const Pod5Error& e) {
+            *rc = ReadsCache();
+            rc->status = e.status;
+            rc->err = e.what();
+        } catch (const std::bad_alloc&) {
+            *rc = ReadsCache();
+            rc->status = PGN_ERR_IO;
+            rc->err = "out of host memory";
+        } catch (const std::exception& e) {
+            *rc = ReadsCache();
+            rc->status = PGN_ERR_CORRUPT;
+            rc->err = e.what();
+        }
+        f.reads = std::move(rc);
+    }
+    if (f.reads->status != PGN_OK) g_err = f.reads->err;
+    return *f.reads;
+}
+
 // The reads table with the reads keepRead[i] (reads in file order) and signal rows renumbered.
 std::vector<uint8_t> filter_reads_table(const IpcReader& r, int iSignal, const std::vector<bool>& keepRead,
                                         const std::vector<int64_t>& remap)
@@ -1300,6 +1496,40 @@ int pgn_pod5_signal_read_batches(const pgn_pod5_file* f, const uint32_t* batch_i
     if (rows_out) *rows_out = row;
     if (data_bytes_out) *data_bytes_out = at;
     if (samples_out) *samples_out = tot;
+    return PGN_OK;
+}
+
+int pgn_pod5_reads_info(const pgn_pod5_file* f, uint64_t* reads, uint32_t* batches, uint64_t* row_entries)
+{
+    if (!f) return PGN_ERR_INVALID_ARG;
+    const ReadsCache& rc = reads_of(*f);
+    if (rc.status != PGN_OK) return rc.status;
+    if (reads) *reads = rc.numSamples.size();
+    if (batches) *batches = rc.batches;
+    if (row_entries) *row_entries = rc.rows.size();
+    return PGN_OK;
+}
+
+int pgn_pod5_reads_read(const pgn_pod5_file* f, uint8_t* read_ids, uint64_t* row_first, uint64_t* rows,
+                        uint64_t* num_samples, uint64_t* signal_samples, float* cal_offset, float* cal_scale,
+                        uint32_t* read_number, uint16_t* channel, uint8_t* well)
+{
+    if (!f) return PGN_ERR_INVALID_ARG;
+    const ReadsCache& rc = reads_of(*f);
+    if (rc.status != PGN_OK) return rc.status;
+    auto put = [](void* dst, const auto& v) {
+        if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+    };
+    put(read_ids, rc.ids);
+    put(row_first, rc.rowFirst);
+    put(rows, rc.rows);
+    put(num_samples, rc.numSamples);
+    put(signal_samples, rc.signalSamples);
+    put(cal_offset, rc.calOffset);
+    put(cal_scale, rc.calScale);
+    put(read_number, rc.readNumber);
+    put(channel, rc.channel);
+    put(well, rc.well);
     return PGN_OK;
 }
 
@@ -1552,3 +1782,24 @@ int pgn_pod5_write_file_reserved(const char* path, const pgn_pod5_file* source, 
 }
 
 }  // extern "C"
+
+// In-library (pgn_internal.h): where the bytes of signal rows sit in the file image.
+int pgn_pod5_signal_row_spans(const pgn_pod5_file* f, size_t n, const uint64_t* rows, const uint8_t** data,
+                              uint64_t* bytes, uint32_t* samples)
+{
+    if (!f || (n && (!rows || !data || !bytes || !samples))) return PGN_ERR_INVALID_ARG;
+    const uint64_t scale = f->signal_type == PGN_POD5_SIGNAL_UNCOMPRESSED ? 2 : 1;
+    for (size_t i = 0; i < n; i++) {
+        if (rows[i] >= f->rows) return PGN_ERR_INVALID_ARG;
+        const size_t b = (size_t)(std::upper_bound(f->batchFirst.begin(), f->batchFirst.end(), rows[i]) -
+                                  f->batchFirst.begin()) - 1;
+        const SignalBatch& sb = f->batches[b];
+        const uint64_t r = rows[i] - f->batchFirst[b];
+        const uint64_t a0 = (uint64_t)ld_i64(sb.offsets + 8 * r) * scale, a1 = (uint64_t)ld_i64(sb.offsets + 8 * r + 8) * scale;
+        // parse_signal_table checked the batch's first and last offsets and that they rise
+        data[i] = sb.data + a0;
+        bytes[i] = a1 - a0;
+        memcpy(&samples[i], (const uint8_t*)sb.samples + 4 * r, 4);
+    }
+    return PGN_OK;
+}

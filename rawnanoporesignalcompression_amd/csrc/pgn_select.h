@@ -422,6 +422,44 @@ __global__ void expand_reads_kernel(uint64_t nreads, const uint64_t* __restrict_
     readN[r] = acc;
 }
 
+// The same for the calibrated decode (pgn_decompress_reads_device_pa): a chunk carries its read's
+// calibration.  calOffset / calScale are NULL together (int16 output: nothing to expand).
+__global__ void expand_reads_pa_kernel(uint64_t nreads, const uint64_t* __restrict__ firstChunk,
+                                       const uint64_t* __restrict__ readOut, const uint32_t* __restrict__ counts,
+                                       const float* __restrict__ calOffset, const float* __restrict__ calScale,
+                                       uint64_t* __restrict__ chunkOut, float* __restrict__ chunkOffset,
+                                       float* __restrict__ chunkScale)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nreads) return;
+    uint64_t acc = 0;
+    const uint64_t base = readOut[r];
+    const float off = calOffset ? calOffset[r] : 0.0f, scale = calScale ? calScale[r] : 0.0f;
+    for (uint64_t c = firstChunk[r]; c < firstChunk[r + 1]; c++) {
+        chunkOut[c] = base + acc;
+        if (calOffset) {
+            chunkOffset[c] = off;
+            chunkScale[c] = scale;
+        }
+        acc += counts[c];
+    }
+}
+
+// A read's status: its first chunk status that is not PGN_OK, in chunk order (PGN_OK without chunks).
+__global__ void reads_status_kernel(uint64_t nreads, const uint64_t* __restrict__ firstChunk,
+                                    const int32_t* __restrict__ chunkStatus, int32_t* __restrict__ readStatus)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nreads) return;
+    int32_t s = PGN_OK;
+    for (uint64_t c = firstChunk[r]; c < firstChunk[r + 1]; c++)
+        if (chunkStatus[c] != PGN_OK) {
+            s = chunkStatus[c];
+            break;
+        }
+    readStatus[r] = s;
+}
+
 // ---- the elementwise pass: out = ((float)adc + (-centre)) * inv -----------------------------------
 // binary32 -> binary16 bits, round to nearest even, of the rounded binary32 product: the empty asm keeps
 // the compiler from fusing multiply and conversion into one rounding (v_fma_mixlo_f16, see pgn_c5.h).

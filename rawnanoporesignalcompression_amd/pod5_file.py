@@ -8,6 +8,10 @@ with the signal column decoded and re-encoded by batched GPU launches.
 
 * :class:`Pod5File` -- footer strings, embedded files, and the signal table as numpy arrays
   (read ids, samples, byte offsets, signal bytes);
+* :meth:`Pod5File.reads` -- the reads table as numpy arrays (which signal rows make which read, and each
+  read's calibration), and :meth:`Pod5File.load_reads` -- whole reads decoded into HBM as ADC counts,
+  calibrated pA or normalised signal (``pod5_get_read_complete_signal``, c_api.h:489-502, and
+  ``ReadRecord.signal`` / ``signal_pa``, reader.py:356-368, for many reads at once, on the device);
 * :func:`write_pod5` -- a combined file from signal-table rows, copying the other tables of a source;
 * :func:`transcode_pod5` -- the GPU transcoder (a HIP device is required; there is no CPU path); with a
   ``torch.distributed`` group of several ranks (one per GPU) the record batches are shared
@@ -56,6 +60,57 @@ class SignalTable:
 
     def blob(self, i: int) -> bytes:
         return self.data[self.offsets[i]:self.offsets[i + 1]].tobytes()
+
+
+@dataclass
+class ReadsTable:
+    """The reads table's flat columns, every record batch in order (pgn_pod5_reads_read)."""
+    read_id: np.ndarray             # (reads, 16) uint8
+    row_first: np.ndarray           # (reads + 1,) uint64: read r lists rows[row_first[r]:row_first[r + 1]]
+    rows: np.ndarray                # uint64 signal-table row indices, read order
+    num_samples: np.ndarray         # (reads,) uint64, the column as stored
+    signal_samples: np.ndarray      # (reads,) uint64, the sum of the rows' `samples`: the read's length
+    calibration_offset: np.ndarray  # (reads,) float32
+    calibration_scale: np.ndarray   # (reads,) float32
+    read_number: np.ndarray         # (reads,) uint32
+    channel: np.ndarray             # (reads,) uint16
+    well: np.ndarray                # (reads,) uint8
+    batches: int = 0                # record batches of the table
+
+    def __len__(self) -> int:
+        return int(self.num_samples.size)
+
+    def index_of(self, read_ids) -> np.ndarray:
+        """The table indices of the given reads: 16-byte ids (bytes, or a (k, 16) uint8 array) or UUID
+        strings, one or a sequence of them; ``KeyError`` for an id the table does not hold."""
+        import uuid
+
+        if isinstance(read_ids, (bytes, bytearray, str, uuid.UUID)):
+            read_ids = [read_ids]
+        index = {self.read_id[i].tobytes(): i for i in range(len(self))}
+        out = np.empty(len(read_ids), np.uint64)
+        for k, rid in enumerate(read_ids):
+            if isinstance(rid, str):
+                key = uuid.UUID(rid).bytes
+            elif isinstance(rid, uuid.UUID):
+                key = rid.bytes
+            else:
+                key = np.asarray(rid, np.uint8).tobytes() if isinstance(rid, np.ndarray) else bytes(rid)
+            if key not in index:
+                raise KeyError(str(uuid.UUID(bytes=key)) if len(key) == 16 else repr(rid))
+            out[k] = index[key]
+        return out
+
+
+@dataclass
+class LoadedReads:
+    """What :meth:`Pod5File.load_reads` leaves on the device."""
+    out: "object"        # torch tensor on the codec's device: read r is out[offsets[r] : offsets[r] + counts[r]]
+    offsets: np.ndarray  # (nreads,) uint64 elements
+    counts: np.ndarray   # (nreads,) uint64 samples
+    status: "object"     # torch.int32 device tensor: each read's first chunk status that is not 0
+    stats: "object"      # codec.ReadStats for output="norm", else None
+    adc: "object" = None  # output="norm": the int16 samples at the same offsets when a buffer held them
 
 
 class Pod5File:
@@ -138,6 +193,134 @@ class Pod5File:
         if rc:
             raise Pod5FileError(rc, f"batches {ids_arr.tolist()} of {self.path}")
         return SignalTable(ids, samples, offs, data, self.signal_type)
+
+    def reads(self) -> ReadsTable:
+        """The reads table (parsed natively on first use; :class:`Pod5FileError` with status 9 when the
+        file has none or keeps an older layout, naming the column)."""
+        n, nb, ne = C.c_uint64(), C.c_uint32(), C.c_uint64()
+        rc = self._lib.pgn_pod5_reads_info(self._h, C.byref(n), C.byref(nb), C.byref(ne))
+        if rc:
+            raise Pod5FileError(rc, f"reads table of {self.path}")
+        n, ne = n.value, ne.value
+        t = ReadsTable(np.empty((n, 16), np.uint8), np.zeros(n + 1, np.uint64), np.empty(ne, np.uint64),
+                       np.empty(n, np.uint64), np.empty(n, np.uint64), np.empty(n, np.float32), np.empty(n, np.float32),
+                       np.empty(n, np.uint32), np.empty(n, np.uint16), np.empty(n, np.uint8), nb.value)
+        rc = self._lib.pgn_pod5_reads_read(self._h, _ptr(t.read_id), t.row_first.ctypes.data, _ptr(t.rows),
+                                           _ptr(t.num_samples), _ptr(t.signal_samples), _ptr(t.calibration_offset),
+                                           _ptr(t.calibration_scale), _ptr(t.read_number), _ptr(t.channel), _ptr(t.well))
+        if rc:
+            raise Pod5FileError(rc, f"reads table of {self.path}")
+        return t
+
+    def load_reads(self, codec, reads=None, output: str = "pa", dtype=None, out=None, out_offsets=None,
+                   stream: int | None = None, row_lists=None, calibration=None, adc=None, **norm_params) -> LoadedReads:
+        """Whole reads of this file decoded into the memory of ``codec``'s device (pgn_pod5_load_reads_device).
+
+        reads: table indices (any order, repeats allowed; ``None``: every read in table order); use
+        ``self.reads().index_of(ids)`` for read ids.  output: ``"adc"`` (int16 counts), ``"pa"``
+        (``(adc + offset) * scale`` with the read's calibration; float32 default or float16) or ``"norm"``
+        (the read normalised by its own statistics, ``**norm_params`` as in
+        :meth:`PGNanoCodec.decompress_reads_norm`; float16 default or float32).  out / out_offsets: the
+        destination (of ``dtype``, on the device) and each read's first element in it (a host sequence;
+        default: packed in call order); ``out`` and the float32 normalisation's int16 workspace are allocated
+        here when not given -- the host knows every read's length.  The codec of the signal column is the
+        file's; ``codec.variant`` decodes ``pgnano.signal``.  row_lists=(row_first, rows) with
+        calibration=(offset, scale) per read (needed for "pa" only) loads the caller's own row lists instead
+        (pgn_pod5_load_row_lists_device: a file without a reads table works).  The result is ready on the
+        caller's current stream."""
+        import torch
+
+        from .codec import ReadStats, _require_device
+        from .codec import norm_params as make_norm
+
+        if output not in _native.LOAD_KINDS:
+            raise ValueError(f"output must be one of {sorted(_native.LOAD_KINDS)} (got {output!r})")
+        default = {"adc": torch.int16, "pa": torch.float32, "norm": torch.float16}[output]
+        dtype = default if dtype is None else dtype
+        allowed = (torch.int16,) if output == "adc" else (torch.float32, torch.float16)
+        if dtype not in allowed:
+            raise ValueError(f"output={output!r} needs dtype in {allowed} (got {dtype})")
+        if norm_params and output != "norm":
+            raise ValueError(f"normalisation parameters {sorted(norm_params)} need output='norm'")
+        prm = make_norm(**norm_params) if output == "norm" else None
+        types = {torch.int16: _native.PGN_OUT_INT16, torch.float32: _native.PGN_OUT_F32,
+                 torch.float16: _native.PGN_OUT_F16}
+        # the reads' lengths, on the host
+        _, samples = self.row_columns()
+        if row_lists is not None:
+            if reads is not None:
+                raise ValueError("give reads or row_lists, not both")
+            first = np.ascontiguousarray(row_lists[0], np.uint64)
+            rows = np.ascontiguousarray(row_lists[1], np.uint64)
+            nreads = first.size - 1
+            if nreads < 0:
+                raise ValueError("row_first needs nreads + 1 entries")
+            cal = [None, None]
+            if calibration is not None:
+                cal = [np.ascontiguousarray(c, np.float32) for c in calibration]
+                if any(c.size != nreads for c in cal):
+                    raise ValueError(f"calibration must have one entry per read ({nreads})")
+            elif output == "pa":
+                raise ValueError("output='pa' with row_lists needs calibration=(offset, scale)")
+            sel_first, sel_rows = first, rows
+        else:
+            table = self.reads()
+            idx = None if reads is None else np.ascontiguousarray(reads, np.uint64)
+            if idx is not None and idx.size and int(idx.max()) >= len(table):
+                raise ValueError(f"read index {int(idx.max())} is beyond the table's {len(table)} reads")
+            nreads = len(table) if idx is None else int(idx.size)
+            sel = np.arange(len(table), dtype=np.int64) if idx is None else idx.astype(np.int64)
+            sel_first, sel_rows = table.row_first, table.rows
+        if sel_rows.size and int(sel_rows.max()) >= samples.size:
+            raise ValueError(f"row index {int(sel_rows.max())} is beyond the signal table's {samples.size} rows")
+        row_end = np.zeros(sel_rows.size + 1, np.uint64)
+        np.cumsum(samples[sel_rows.astype(np.int64)], out=row_end[1:], dtype=np.uint64)
+        per_read = (row_end[sel_first[1:].astype(np.int64)] - row_end[sel_first[:-1].astype(np.int64)]).astype(np.uint64)
+        counts = per_read if row_lists is not None else per_read[sel]
+        if out_offsets is None:
+            offs = None
+            need = int(counts.sum())
+        else:
+            offs = np.ascontiguousarray(out_offsets, np.uint64)
+            if offs.size != nreads:
+                raise ValueError(f"out_offsets must have one entry per read ({nreads})")
+            need = int((offs + counts).max()) if nreads else 0
+        dev = torch.device("cuda", codec.device)
+        for t, name, want in ((out, "out", dtype), (adc, "adc", torch.int16)):
+            if t is not None:
+                _require_device(t, name, codec.device)
+                if t.dtype != want:
+                    raise ValueError(f"{name} must have dtype {want} (got {t.dtype})")
+        caller = torch.cuda.current_stream()
+        ls = codec._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            if out is None:
+                out = torch.empty(max(need, 1), dtype=dtype, device=dev)
+            if adc is None and output == "norm" and dtype == torch.float32:
+                adc = torch.empty(out.numel(), dtype=torch.int16, device=dev)
+            status = torch.full((nreads,), -1, dtype=torch.int32, device=dev)
+            raw = (torch.zeros((nreads, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
+                   if output == "norm" else None)
+            got_off, got_n = np.zeros(nreads, np.uint64), np.zeros(nreads, np.uint64)
+            args = _native.LoadArgs(_native.LOAD_KINDS[output], types[dtype], _native.VARIANTS[codec.variant], 0,
+                                    C.pointer(prm) if prm is not None else None, out.data_ptr(), out.numel(),
+                                    _ptr(offs) or None, adc.data_ptr() if adc is not None else None,
+                                    raw.data_ptr() if raw is not None and nreads else None,
+                                    status.data_ptr() if nreads else None, _ptr(got_off) or None, _ptr(got_n) or None)
+            lib = codec._lib
+            if row_lists is not None:
+                rc = lib.pgn_pod5_load_row_lists_device(codec._h, self._h, nreads, sel_first.ctypes.data, _ptr(sel_rows),
+                                                        _ptr(cal[0]), _ptr(cal[1]), C.byref(args), ls.cuda_stream)
+            else:
+                # NULL means every read: an empty selection still passes a pointer
+                sel_ptr = None if idx is None else (idx if idx.size else np.zeros(1, np.uint64)).ctypes.data
+                rc = lib.pgn_pod5_load_reads_device(codec._h, self._h, sel_ptr, nreads, C.byref(args), ls.cuda_stream)
+            if rc:
+                from .codec import PGNanoError
+
+                raise PGNanoError(rc, lib.pgn_pod5_last_error().decode(errors="replace"))
+        caller.wait_stream(ls)
+        return LoadedReads(out, got_off, got_n, status, ReadStats(raw) if raw is not None else None, adc)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
