@@ -310,8 +310,9 @@ int pgn_read_stats_device(pgn_ctx *ctx, size_t nreads, const int16_t *d_samples,
  * call gives; a read's status is its first chunk status that is not PGN_OK, in chunk order, and the
  * output and stats of such a read are unspecified.  Nothing is written outside
  * [d_read_out_offsets[r], + n_r) of any read.
- * Not covered: adapter trimming, bfloat16, the host-memory per-chunk calls, a read shared by several
- * workgroups (one workgroup selects one read).  The read -> chunk map of a POD5 file comes from
+ * Not covered: adapter trimming (that is pgn_segment_reads_device, "Trimmed, normalised model segments"
+ * below), bfloat16, the host-memory per-chunk calls, a read shared by several workgroups (one workgroup
+ * selects one read).  The read -> chunk map of a POD5 file comes from
  * pgn_pod5_reads_read, and pgn_pod5_load_reads_device (pgnano_pod5file.h) makes this call from a file. */
 int pgn_decompress_reads_device_norm(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nreads,
                                      size_t nchunks, const uint64_t *d_read_first_chunk, const uint8_t *d_in,
@@ -347,6 +348,90 @@ int pgn_decompress_reads_device_pa(pgn_ctx *ctx, int codec, uint32_t max_chunk_s
  * ordered after the context's earlier calls. */
 int pgn_reads_status_device(pgn_ctx *ctx, size_t nreads, const uint64_t *d_read_first_chunk,
                             const int32_t *d_chunk_status, int32_t *d_read_status, void *stream);
+
+/* ---- Trimmed, normalised model segments -------------------------------------------------------------
+ * The last two steps before a basecaller's model: cut the adapter head off each read, normalise what is
+ * left by its own statistics, and lay it out as rows of a [segments, L] tensor of fixed-length, overlapping
+ * pieces.  One call takes decoded int16 reads on the device and leaves that tensor and its index there.
+ * Every output is exact; the definitions below are the contract.  (The trim is the windowed-threshold head
+ * trim that basecaller front ends use; no such source was at hand to compare with, so this text defines it.)
+ * A read is x[0..n), int16.
+ *
+ * Trim (pgn_trim_params; usual values max_samples 8000, window 40, min_elements 3, min_trim 10, mad_mult
+ * 1.4826, threshold_mads 2.4 -- the C ABI has no defaults):
+ *   max_samples == 0   trim = 0: trimming is off and no head statistics are taken
+ *   H = min(n, max_samples).  H < min_trim + window: no complete window, trim = min(min_trim, n)
+ *   otherwise          m2 and mad4 are those of the head x[0..H), as the per-read normalisation section
+ *                      defines them (the same selection computes them), and in binary32, one rounding per
+ *                      operation and no FMA:
+ *                        centre_h = 0.5f * (float)m2
+ *                        spread_h = mad_mult * (0.25f * (float)mad4)        (no floor)
+ *                        thr      = centre_h + threshold_mads * spread_h
+ *                      A sample is "above" when (float)x[i] > thr.
+ *                      W = (H - min_trim) / window windows; window w covers [s, e), s = min_trim + w * window,
+ *                      e = s + window.  Scan w = 0 .. W-1 with seen = false:
+ *                        if seen, or the window has more than min_elements samples above: seen = true, and
+ *                          if x[e-1] is above, go on to the next window;
+ *                          otherwise stop: trim = e if e < H, else min_trim
+ *                        (a window before the first such peak never stops the scan)
+ *                      If the scan ends without stopping, trim = min_trim.
+ * Normalisation: pgn_norm_params and the statistics as in the per-read section, taken over y = x[trim..n),
+ * m = n - trim samples.  The value is that section's ((float)adc + (-centre)) * (1.0f / spread); PGN_OUT_F16
+ * is that value converted once.
+ * Segments (pgn_segment_params: length L, overlap V, 0 <= V < L, 1 <= L <= 2^24; stride S = L - V):
+ *   m == 0   no segment
+ *   m <= L   one segment, start 0, valid = m
+ *   m > L    k = ceil((m - L) / S) + 1 segments; segment j starts at min(j * S, m - L) with valid = L, so
+ *            the last one ends at the read's end
+ * A segment's row is y[start .. start + valid) normalised; elements [valid, L) are +0.0 (all bits zero).
+ * Segments are numbered in read order, then start order.  segments(m) does not decrease as m grows, so the
+ * count taken from the untrimmed n is an upper bound the host can compute without a wait.
+ *
+ * pgn_read_segments (one per read): its segments are [first_segment, + nsegments); head_m2, head_mad4 and
+ * threshold are 0 where no head statistics were taken.  pgn_segment (one per segment): `start` is the sample
+ * index in the untrimmed read (it includes trim).
+ * A read's status is d_read_status_in[r] if that array is given and the entry is not PGN_OK; otherwise what
+ * the statistics give (n >= 2^32: PGN_ERR_UNSUPPORTED; such a read is not trimmed).
+ * A read whose status is not PGN_OK produces no segments; one with a bad input status is not trimmed, and
+ * its d_stats entry is unspecified.
+ * A segment whose index is at or above segment_capacity is not written, neither its row nor its table
+ * entry; every read that has one gets PGN_ERR_DST_TOO_SMALL (its first_segment and nsegments are still
+ * what they would be), and *d_total is the number needed.  Nothing is written outside rows
+ * [0, min(total, segment_capacity)) of d_out.  With segment_capacity == 0, d_out and d_segments may be NULL.
+ * d_stats (optional) receives the statistics of the trimmed reads, d_total (optional) the segment count.
+ * Asynchronous on `stream`, no host wait; the work arrays live in context scratch that grows with nreads.
+ * PGN_ERR_INVALID_ARG before any GPU call, checking in this order: a NULL ctx or a NULL params struct; the
+ * norm parameters as in the per-read section; window < 1 with max_samples > 0, a non-finite mad_mult or
+ * threshold_mads; L or V outside the ranges above; out_type not PGN_OUT_F32 or PGN_OUT_F16; then, for
+ * nreads > 0, a missing array, or nreads >= 2^32.
+ * Not covered: a decode-fused entry point (the norm call is decode, then statistics, then a pass, so this
+ * call after an int16 decode costs the same); bfloat16; a maximum-trim fraction or a rejection of
+ * over-trimmed reads; front padding; one read shared by several workgroups in the selection. */
+typedef struct pgn_trim_params {
+    uint32_t max_samples, window, min_elements, min_trim;
+    float mad_mult, threshold_mads;
+} pgn_trim_params;
+typedef struct pgn_segment_params {
+    uint32_t length, overlap;
+} pgn_segment_params;
+typedef struct pgn_read_segments {
+    uint64_t first_segment;
+    uint32_t nsegments, trim;
+    int32_t status;
+    int32_t head_m2;
+    uint32_t head_mad4;
+    float threshold;
+} pgn_read_segments;
+typedef struct pgn_segment {
+    uint32_t read, start, valid, pad;
+} pgn_segment;
+
+int pgn_segment_reads_device(pgn_ctx *ctx, size_t nreads, const int16_t *d_samples, const uint64_t *d_read_offsets,
+                             const uint64_t *d_read_counts, const int32_t *d_read_status_in,
+                             const pgn_trim_params *trim, const pgn_norm_params *norm,
+                             const pgn_segment_params *segment, void *d_out, int out_type, uint64_t segment_capacity,
+                             pgn_segment *d_segments, pgn_read_segments *d_reads, pgn_read_stats *d_stats,
+                             uint64_t *d_total, void *stream);
 
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->

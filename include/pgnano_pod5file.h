@@ -161,7 +161,8 @@ int pgn_pod5_write_file_keep_going(const char *path, const pgn_pod5_file *source
  *   PGN_ERR_CORRUPT      malformed Arrow, list offsets that do not rise, a listed row >= the signal
  *                        table's rows
  * Not covered: older reads-table layouts, the run-info table's contents (and the reads' dictionary
- * columns that point into it), adapter trimming, writing a reads table from scratch. */
+ * columns that point into it), adapter trimming (pgn_segment_reads_device over the loaded reads,
+ * pgnano_hip.h "Trimmed, normalised model segments"), writing a reads table from scratch. */
 int pgn_pod5_reads_info(const pgn_pod5_file *f, uint64_t *reads, uint32_t *batches, uint64_t *row_entries);
 /* Any pointer may be NULL.  read r lists signal rows rows[row_first[r] .. row_first[r + 1]);
  * signal_samples[r] is the sum of those rows' `samples` (pod5_get_read_complete_sample_count): the

@@ -52,6 +52,28 @@ class ReadStats(C.Structure):
                 ("mad4", C.c_uint32), ("centre", C.c_float), ("spread", C.c_float)]
 
 
+class TrimParams(C.Structure):
+    """pgn_trim_params"""
+    _fields_ = [("max_samples", C.c_uint32), ("window", C.c_uint32), ("min_elements", C.c_uint32),
+                ("min_trim", C.c_uint32), ("mad_mult", C.c_float), ("threshold_mads", C.c_float)]
+
+
+class SegmentParams(C.Structure):
+    """pgn_segment_params"""
+    _fields_ = [("length", C.c_uint32), ("overlap", C.c_uint32)]
+
+
+class ReadSegments(C.Structure):
+    """pgn_read_segments"""
+    _fields_ = [("first_segment", C.c_uint64), ("nsegments", C.c_uint32), ("trim", C.c_uint32), ("status", C.c_int32),
+                ("head_m2", C.c_int32), ("head_mad4", C.c_uint32), ("threshold", C.c_float)]
+
+
+class Segment(C.Structure):
+    """pgn_segment"""
+    _fields_ = [("read", C.c_uint32), ("start", C.c_uint32), ("valid", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -108,6 +130,9 @@ SIGNATURES = [
      [_VP, C.c_int, C.c_uint32, _SZ, _SZ, _U64P, _VP, _U64P, _U64P, _U32P, _VP, C.c_int, _U64P, _VP, _VP, _I32P, _I32P,
       _VP]),
     ("pgn_reads_status_device", C.c_int, [_VP, _SZ, _U64P, _I32P, _I32P, _VP]),
+    ("pgn_segment_reads_device", C.c_int,
+     [_VP, _SZ, _VP, _U64P, _U64P, _I32P, C.POINTER(TrimParams), C.POINTER(NormParams), C.POINTER(SegmentParams), _VP,
+      C.c_int, C.c_uint64, _VP, _VP, _VP, _U64P, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

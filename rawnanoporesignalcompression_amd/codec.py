@@ -22,6 +22,8 @@ device-resident torch tensors: one launch encodes or decodes every chunk of a ba
 (float32 or float16 pA; :func:`calibrate_signal` is the same arithmetic on the host).
 :meth:`PGNanoCodec.decompress_reads_norm` decodes whole reads and writes each normalised by its own
 quantiles or median / MAD; :meth:`PGNanoCodec.read_stats` gives those statistics for decoded reads.
+:meth:`PGNanoCodec.segment_reads` trims the head of decoded reads, normalises them and cuts them into the
+``[segments, length]`` tensor a model reads (:func:`trim_signal` and :func:`segment_signal` on the host).
 """
 from __future__ import annotations
 
@@ -121,6 +123,174 @@ def norm_params(mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.5
         raise ValueError(f"mode must be one of {sorted(_native.NORM_MODES)} (got {mode!r})")
     return _native.NormParams(_native.NORM_MODES[mode], 0, float(p[0]), float(p[1]), float(centre_mult),
                               float(spread_mult), float(spread_floor), 0.0)
+
+
+class _Columns:
+    """Named column views over one device tensor of C structs (``raw``: uint8, records x struct bytes), as
+    :class:`ReadStats` has them: views, no copies; unsigned 32-bit fields come as int32 (their bits).
+    :meth:`numpy` gives the same as a structured host array."""
+
+    DTYPE = None
+    _COLS = {}
+
+    def __init__(self, raw):
+        self.raw = raw
+
+    def __len__(self):
+        return int(self.raw.shape[0])
+
+    def __getattr__(self, name):
+        import torch
+
+        cols = type(self)._COLS
+        if name in cols:
+            t, col = cols[name]
+            return self.raw.view(getattr(torch, t))[:, col]
+        raise AttributeError(name)
+
+    def numpy(self):
+        return self.raw.cpu().numpy().reshape(-1).view(type(self).DTYPE)
+
+
+class ReadSegments(_Columns):
+    """``pgn_read_segments`` of every read: ``first_segment`` int64, ``nsegments``, ``trim``, ``status``,
+    ``head_m2``, ``head_mad4`` int32, ``threshold`` float32."""
+
+    DTYPE = np.dtype([("first_segment", "<u8"), ("nsegments", "<u4"), ("trim", "<u4"), ("status", "<i4"),
+                      ("head_m2", "<i4"), ("head_mad4", "<u4"), ("threshold", "<f4")])
+    _COLS = {"first_segment": ("int64", 0), "nsegments": ("int32", 2), "trim": ("int32", 3), "status": ("int32", 4),
+             "head_m2": ("int32", 5), "head_mad4": ("int32", 6), "threshold": ("float32", 7)}
+
+
+class SegmentTable(_Columns):
+    """``pgn_segment`` of every segment: ``read``, ``start`` (in the untrimmed read) and ``valid``, int32."""
+
+    DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("valid", "<u4"), ("pad", "<u4")])
+    _COLS = {"read": ("int32", 0), "start": ("int32", 1), "valid": ("int32", 2)}
+
+
+@dataclass
+class SegmentedReads:
+    """What :meth:`PGNanoCodec.segment_reads` leaves on the device."""
+    out: "object"       # [capacity, length] float16 / float32: rows [0, min(total, capacity)) are written
+    segments: SegmentTable  # capacity entries, the same rows
+    reads: ReadSegments     # one entry per read
+    stats: ReadStats        # of the trimmed reads
+    total: "object"     # int64 device scalar: the segments the batch needs
+
+
+def trim_params(max_samples=8000, window=40, min_elements=3, min_trim=10, mad_mult=1.4826, threshold_mads=2.4):
+    """``pgn_trim_params`` from Python values (the usual values live here; the C ABI has none).
+    ``max_samples=0`` turns trimming off."""
+    return _native.TrimParams(int(max_samples), int(window), int(min_elements), int(min_trim), float(mad_mult),
+                              float(threshold_mads))
+
+
+def _trim_struct(trim):
+    """None / False: trimming off; True: the usual values; a dict: :func:`trim_params` of it; or the struct."""
+    if trim is None or trim is False:
+        return trim_params(max_samples=0)
+    if trim is True:
+        return trim_params()
+    if isinstance(trim, _native.TrimParams):
+        return trim
+    return trim_params(**trim)
+
+
+def segment_params(length, overlap):
+    """``pgn_segment_params``: rows of ``length`` elements, neighbours sharing ``overlap`` of them."""
+    length, overlap = int(length), int(overlap)
+    if not (1 <= length <= 1 << 24 and 0 <= overlap < length):
+        raise ValueError(f"need 1 <= length <= 2^24 and 0 <= overlap < length (got {length}, {overlap})")
+    return _native.SegmentParams(length, overlap)
+
+
+def _segment_starts(m: int, length: int, overlap: int):
+    """[(start, valid)] of a trimmed read of m samples (include/pgnano_hip.h, "Segments")."""
+    stride = length - overlap
+    if m == 0:
+        return []
+    if m <= length:
+        return [(0, m)]
+    k = -(-(m - length) // stride) + 1
+    return [(min(j * stride, m - length), length) for j in range(k)]
+
+
+def segment_bound(counts, length, overlap) -> int:
+    """The segments a batch of reads of these (untrimmed) lengths can need: trimming only shortens a read
+    and the count does not decrease with the length, so this is an upper bound, computed on the host."""
+    p = segment_params(length, overlap)
+    n = np.asarray(counts).astype(np.int64).reshape(-1)
+    stride = p.length - p.overlap
+    k = np.where(n > p.length, (np.maximum(n - p.length, 0) + stride - 1) // stride + 1, (n > 0).astype(np.int64))
+    return int(k.sum())
+
+
+def trim_signal(adc, **trim) -> int:
+    """The head trim of one read on the host (include/pgnano_hip.h, "Trim"): the samples to drop.
+    ``**trim`` as in :func:`trim_params`."""
+    T = trim_params(**trim)
+    x = np.asarray(adc, dtype=np.int16).reshape(-1)
+    n = x.size
+    if T.max_samples == 0:
+        return 0
+    H = min(n, T.max_samples)
+    if H < T.min_trim + T.window:
+        return min(T.min_trim, n)
+    v = x[:H].astype(np.int64)
+    s = np.sort(v)
+    m2 = int(s[(H - 1) // 2] + s[H // 2])
+    t = np.sort(np.abs(2 * v - m2))
+    mad4 = int(t[(H - 1) // 2] + t[H // 2])
+    f32 = np.float32
+    thr = f32(0.5) * f32(m2) + f32(T.threshold_mads) * (f32(T.mad_mult) * (f32(0.25) * f32(mad4)))
+    above = x[:H].astype(np.float32) > thr
+    seen = False
+    for w in range((H - T.min_trim) // T.window):
+        e = T.min_trim + (w + 1) * T.window
+        seen = seen or int(above[e - T.window:e].sum()) > T.min_elements
+        if seen and not above[e - 1]:
+            return e if e < H else T.min_trim
+    return T.min_trim
+
+
+def _host_stats(y, prm):
+    """(centre, spread) of one read on the host, as the per-read normalisation section defines them."""
+    f32 = np.float32
+    s = np.sort(y.astype(np.int64))
+    n = s.size
+    if prm.mode == _native.PGN_NORM_QUANTILE:
+        a = int(s[int(np.floor(np.float64(prm.p_lo) * np.float64(n - 1)))])
+        b = int(s[int(np.floor(np.float64(prm.p_hi) * np.float64(n - 1)))])
+        centre, spread = f32(prm.centre_mult) * f32(a + b), f32(prm.spread_mult) * f32(b - a)
+    else:
+        m2 = int(s[(n - 1) // 2] + s[n // 2])
+        t = np.sort(np.abs(2 * y.astype(np.int64) - m2))
+        centre = f32(0.5) * f32(m2)
+        spread = f32(prm.spread_mult) * (f32(0.25) * f32(int(t[(n - 1) // 2] + t[n // 2])))
+    return centre, max(spread, f32(prm.spread_floor))
+
+
+def segment_signal(adc, length, overlap, trim=None, dtype=np.float16, **norm):
+    """The model segments of one read on the host, ``[segments, length]``: the read without its trimmed head
+    (``trim`` as in :meth:`PGNanoCodec.segment_reads`), normalised by its own statistics (``**norm`` as in
+    :func:`norm_params`; :func:`normalise_signal`'s arithmetic), cut into rows that overlap by ``overlap``, the
+    last aligned to the read's end, a short read padded with +0.0.  :meth:`PGNanoCodec.segment_reads` writes
+    these bits."""
+    p = segment_params(length, overlap)
+    prm = norm_params(**norm)
+    T = _trim_struct(trim)
+    x = np.asarray(adc, dtype=np.int16).reshape(-1)
+    y = x[trim_signal(x, **{f: getattr(T, f) for f, _ in T._fields_}):]
+    plan = _segment_starts(y.size, p.length, p.overlap)
+    rows = np.zeros((len(plan), p.length), dtype)
+    if plan:
+        centre, spread = _host_stats(y, prm)
+        with np.errstate(over="ignore"):  # binary16 overflow is +-inf, as on the device
+            z = normalise_signal(y, centre, spread, dtype)
+        for j, (start, valid) in enumerate(plan):
+            rows[j, :valid] = z[start:start + valid]
+    return rows
 
 
 @dataclass
@@ -408,6 +578,75 @@ class PGNanoCodec:
                                                    _ptr(raw), ls.cuda_stream))
         caller.wait_stream(ls)
         return ReadStats(raw)
+
+    def segment_reads(self, samples, read_offsets, read_counts, *, length, overlap, trim=None, dtype=None,
+                      read_status=None, capacity=None, out=None, stream: int | None = None,
+                      **norm) -> SegmentedReads:
+        """Decoded reads on the device -> the model-input tensor (pgn_segment_reads_device): each read loses its
+        trimmed head, is normalised by the statistics of what is left and cut into rows of ``length`` elements
+        that overlap by ``overlap``; the last row of a read is aligned to its end and a short read is padded with
+        +0.0.  Bit for bit what :func:`segment_signal` gives on the host, read after read.
+
+        Read r is ``samples[read_offsets[r] : read_offsets[r] + read_counts[r]]`` (int16; any start); offsets and
+        counts are tensors or host arrays.  trim: ``None`` / ``False`` for none, ``True`` for the usual head trim,
+        or a dict for :func:`trim_params`.  dtype ``torch.float16`` (default) or ``torch.float32``.
+        ``**norm`` as in :func:`norm_params`.  read_status: int32 per read (e.g. a loader's); a read whose entry
+        is not 0 gives no segments and keeps that status.  capacity: rows of ``out`` (default: ``out``'s, else
+        :func:`segment_bound` of the counts, which copies device counts to the host -- pass it, or host counts,
+        to avoid that wait); segments beyond it are not written and their reads get status 1.  out: a
+        contiguous ``[rows, length]`` tensor of ``dtype``.  No host wait in the call itself: ``total`` and every
+        index stay on the device."""
+        import torch
+
+        dtype = torch.float16 if dtype is None else dtype
+        types = {torch.float32: _native.PGN_OUT_F32, torch.float16: _native.PGN_OUT_F16}
+        if dtype not in types:
+            raise ValueError(f"dtype must be torch.float32 or torch.float16 (got {dtype})")
+        seg, prm, tprm = segment_params(length, overlap), norm_params(**norm), _trim_struct(trim)
+        _require_device(samples, "samples", self.device)
+        if samples.dtype != torch.int16:
+            raise ValueError(f"samples must be int16 (got {samples.dtype})")
+        if out is not None:
+            _require_device(out, "out", self.device)
+            if out.dtype != dtype or out.dim() != 2 or out.shape[1] != seg.length or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous [rows, {seg.length}] tensor of {dtype}")
+            if capacity is not None and int(capacity) > out.shape[0]:
+                raise ValueError(f"capacity {int(capacity)} is beyond out's {out.shape[0]} rows")
+        if capacity is None:
+            host = read_counts.cpu().numpy() if isinstance(read_counts, torch.Tensor) else read_counts
+            capacity = out.shape[0] if out is not None else segment_bound(host, seg.length, seg.overlap)
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        dev = samples.device
+
+        def i64(a):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a).astype(np.int64))
+            return t.to(device=dev, dtype=torch.int64).contiguous()
+
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            ro, rc = i64(read_offsets), i64(read_counts)
+            n = int(rc.numel())
+            if int(ro.numel()) != n:
+                raise ValueError("read_offsets and read_counts must have one entry per read")
+            st_in = None
+            if read_status is not None:
+                st_in = read_status.to(device=dev, dtype=torch.int32).contiguous()
+                if int(st_in.numel()) != n:
+                    raise ValueError(f"read_status must have one entry per read ({n})")
+            if out is None:
+                out = torch.empty((capacity, seg.length), dtype=dtype, device=dev)
+            segs = torch.zeros((capacity, C.sizeof(_native.Segment)), dtype=torch.uint8, device=dev)
+            reads = torch.zeros((n, C.sizeof(_native.ReadSegments)), dtype=torch.uint8, device=dev)
+            raw = torch.zeros((n, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
+            total = torch.zeros((), dtype=torch.int64, device=dev)
+            _check(self._lib.pgn_segment_reads_device(
+                self._h, n, _ptr(samples), _ptr(ro), _ptr(rc), _ptr(st_in), C.byref(tprm), C.byref(prm), C.byref(seg),
+                _ptr(out), types[dtype], capacity, _ptr(segs), _ptr(reads), _ptr(raw), _ptr(total), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return SegmentedReads(out, SegmentTable(segs), ReadSegments(reads), ReadStats(raw), total)
 
     def decompress_reads_norm(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, *,
                               mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0,

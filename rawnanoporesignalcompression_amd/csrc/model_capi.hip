@@ -5,6 +5,7 @@
 #include <string.h>
 
 #define PGN_SELECT_HOST_ONLY
+#include "pgn_segment.h"
 #include "pgn_select.h"
 #include "zstd1_dec.h"
 #include "zstd1_model.h"
@@ -140,6 +141,36 @@ int pgnm_locate(const uint32_t* coarse, const uint32_t* k, int nranks, uint32_t*
         for (int i = 0; i < 2; i++) { bin[i] = p[i].bin; resid[i] = p[i].resid; }
     } else {
         return -1;
+    }
+    return 0;
+}
+
+// The head trim (pgn_segment.h) of one read: the selection above over the head, the threshold and the
+// window scan as the header writes it.  Returns 0, or -1 for parameters the C ABI rejects.
+int pgnm_trim(const int16_t* x, uint64_t n, const pgn_trim_params* prm, uint32_t* trim, int32_t* head_m2,
+              uint32_t* head_mad4, float* threshold)
+{
+    if (!pgn::seg::trim_params_valid(prm) || !trim) return -1;
+    const pgn::seg::TrimResult r = pgn::seg::host_trim(x, n, *prm);
+    *trim = r.trim;
+    if (head_m2) *head_m2 = r.m2;
+    if (head_mad4) *head_mad4 = r.mad4;
+    if (threshold) *threshold = r.thr;
+    return 0;
+}
+
+// The segments of a trimmed read of m samples: *nseg of them, and the first min(*nseg, max) starts and
+// valid counts.  Returns 0, or -1 for parameters the C ABI rejects.
+int pgnm_segment_plan(uint64_t m, const pgn_segment_params* prm, uint64_t* nseg, uint64_t max, uint64_t* start,
+                      uint32_t* valid)
+{
+    using namespace pgn::seg;
+    if (!segment_params_valid(prm) || !nseg) return -1;
+    const uint32_t L = prm->length, S = prm->length - prm->overlap;
+    *nseg = segment_count(m, L, S);
+    for (uint64_t j = 0; j < *nseg && j < max; j++) {
+        start[j] = segment_start(m, L, S, j);
+        valid[j] = segment_valid(m, L);
     }
     return 0;
 }

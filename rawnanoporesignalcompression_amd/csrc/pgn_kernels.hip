@@ -18,6 +18,7 @@
 #include "../../include/pgnano_pod5.h"
 #include "pgn_c5.h"
 #include "pgn_internal.h"
+#include "pgn_segment.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2125,6 +2126,10 @@ struct pgn_ctx {
     float* paChunkOffset = nullptr;
     float* paChunkScale = nullptr;
     size_t paChunks = 0;
+    // pgn_segment_reads_device: per read the head count, the trimmed offset and count, the head's and the
+    // trimmed read's statistics; then the segment total (one block, carved up by ensure_segment)
+    uint8_t* segWork = nullptr;
+    size_t segReads = 0;
     // an object of another translation unit (the POD5 loader's staging, pgn_internal.h)
     void* ext = nullptr;
     void (*extDestroy)(void*) = nullptr;
@@ -2314,6 +2319,7 @@ int pgn_ctx_destroy(pgn_ctx* c)
     (void)hipFree(c->normChunkRead);
     (void)hipFree(c->normReadN);
     (void)hipFree(c->normStats);
+    (void)hipFree(c->segWork);
     if (c->largeHdrHost) (void)hipHostFree(c->largeHdrHost);
     for (hipEvent_t e : {c->evScanFork, c->evScan})
         if (e) (void)hipEventDestroy(e);
@@ -3480,6 +3486,119 @@ extern "C" int pgn_reads_status_device(pgn_ctx* c, size_t nreads, const uint64_t
     HIPCHK(hipEventRecord(c->evLast, s));
     c->haveLast = true;
     return rc;
+}
+
+// ---- trimmed, normalised model segments (pgn_segment.h) -----------------------------------------
+struct SegWork {
+    uint64_t* headN;
+    uint64_t* trimOffsets;
+    uint64_t* trimCounts;
+    pgn_read_stats* headStats;
+    pgn_read_stats* stats;
+    uint64_t* total;
+};
+
+static int ensure_segment(pgn_ctx* c, size_t nreads, SegWork& w)
+{
+    if (nreads > c->segReads) {
+        wait_last_host(c);
+        (void)hipFree(c->segWork);
+        c->segWork = nullptr;
+        c->segReads = 0;
+        HIPCHK(hipMalloc(&c->segWork, nreads * (3 * sizeof(uint64_t) + 2 * sizeof(pgn_read_stats)) + sizeof(uint64_t)));
+        c->segReads = nreads;
+    }
+    const size_t R = c->segReads;
+    w.headN = reinterpret_cast<uint64_t*>(c->segWork);
+    w.trimOffsets = w.headN + R;
+    w.trimCounts = w.trimOffsets + R;
+    w.headStats = reinterpret_cast<pgn_read_stats*>(w.trimCounts + R);
+    w.stats = w.headStats + R;
+    w.total = reinterpret_cast<uint64_t*>(w.stats + R);
+    return PGN_OK;
+}
+
+extern "C" int pgn_segment_reads_device(pgn_ctx* c, size_t nreads, const int16_t* d_samples, const uint64_t* d_read_offsets,
+                                        const uint64_t* d_read_counts, const int32_t* d_read_status_in,
+                                        const pgn_trim_params* trim, const pgn_norm_params* norm,
+                                        const pgn_segment_params* segment, void* d_out, int out_type,
+                                        uint64_t segment_capacity, pgn_segment* d_segments, pgn_read_segments* d_reads,
+                                        pgn_read_stats* d_stats, uint64_t* d_total, void* stream)
+{
+    if (!c || !trim || !norm || !segment) return PGN_ERR_INVALID_ARG;
+    if (!sel::params_valid(norm) || !seg::trim_params_valid(trim) || !seg::segment_params_valid(segment))
+        return PGN_ERR_INVALID_ARG;
+    if (out_type != PGN_OUT_F32 && out_type != PGN_OUT_F16) return PGN_ERR_INVALID_ARG;
+    if (nreads) {
+        if (!d_samples || !d_read_offsets || !d_read_counts || !d_reads) return PGN_ERR_INVALID_ARG;
+        if (segment_capacity && (!d_out || !d_segments)) return PGN_ERR_INVALID_ARG;
+        if (nreads > 0xFFFFFFFFull) return PGN_ERR_INVALID_ARG;  // a segment's read index is 32-bit
+    }
+    if (nreads == 0 && !d_total) return PGN_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    if (nreads == 0) {
+        HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    SegWork w;
+    int rc = ensure_segment(c, nreads, w);
+    if (rc != PGN_OK) return rc;
+    const size_t cus = (size_t)(c->numCUs > 0 ? c->numCUs : 1);
+    const unsigned perRead = (unsigned)((nreads + 255) / 256);
+    const unsigned waveGrid = (unsigned)std::min<size_t>((nreads + 3) / 4, cus * 64);
+    const bool trimOn = trim->max_samples > 0;
+    const uint64_t* offsets = d_read_offsets;
+    const uint64_t* counts = d_read_counts;
+    if (trimOn) {
+        const seg::TrimArgs ta{d_samples, d_read_offsets, d_read_counts, d_read_status_in, nreads, *trim, w.headN,
+                               w.headStats, d_reads, w.trimOffsets, w.trimCounts};
+        hipLaunchKernelGGL(seg::trim_heads_kernel, dim3(perRead), dim3(256), 0, s, ta);
+        HIPCHK(hipGetLastError());
+        // med/MAD of the heads: only m2 and mad4 are used, so the float parameters are placeholders
+        const pgn_norm_params headPrm{PGN_NORM_MEDMAD, 0, 0.0, 1.0, 1.0f, 1.0f, 1.0f, 0.0f};
+        const sel::StatsArgs ha{d_samples, d_read_offsets, w.headN, nreads, headPrm, w.headStats, nullptr, nullptr};
+        rc = launch_read_stats(c, ha, s);
+        if (rc != PGN_OK) return rc;
+        hipLaunchKernelGGL(seg::trim_kernel, dim3(waveGrid), dim3(256), 0, s, ta);
+        HIPCHK(hipGetLastError());
+        offsets = w.trimOffsets;
+        counts = w.trimCounts;
+    }
+    pgn_read_stats* stats = d_stats ? d_stats : w.stats;
+    const sel::StatsArgs sa{d_samples, offsets, counts, nreads, *norm, stats, nullptr, nullptr};
+    rc = launch_read_stats(c, sa, s);
+    if (rc != PGN_OK) return rc;
+    const uint32_t L = segment->length, S = segment->length - segment->overlap;
+    const seg::PlanArgs pa{nreads, d_read_status_in, stats, d_reads, w.total, d_total, segment_capacity, L, S, trimOn ? 0u : 1u};
+    hipLaunchKernelGGL(seg::segment_scan_kernel, dim3(1), dim3(seg::kScanThreads), 0, s, pa);
+    HIPCHK(hipGetLastError());
+    if (segment_capacity) {
+        const seg::TableArgs tb{nreads, d_reads, stats, d_segments, segment_capacity, L, S};
+        hipLaunchKernelGGL(seg::segment_table_kernel, dim3(waveGrid), dim3(256), 0, s, tb);
+        HIPCHK(hipGetLastError());
+        // a row is shared by the smallest power of two of threads that covers its 16-byte units, up to the
+        // workgroup; longer rows are split over up to kWriteSplit workgroups of four or more passes each
+        const uint32_t unit = out_type == PGN_OUT_F32 ? seg::kUnit<float> : seg::kUnit<_Float16>;
+        const uint32_t units = (L + unit - 1) / unit;
+        uint32_t log2Tpr = 0;
+        while (log2Tpr < 8 && (1u << log2Tpr) < units) log2Tpr++;
+        const uint32_t rowsPerBlock = seg::kWriteThreads >> log2Tpr;
+        const uint32_t split = std::min<uint32_t>(seg::kWriteSplit, std::max<uint32_t>(1, units / (4 * seg::kWriteThreads)));
+        const uint64_t blocks = (segment_capacity + rowsPerBlock - 1) / rowsPerBlock;
+        const dim3 grid((unsigned)std::min<uint64_t>(blocks, 1u << 20), split);
+        const seg::WriteArgs wa{d_samples, d_read_offsets, stats, d_segments, w.total, d_out, segment_capacity, L, log2Tpr};
+        if (out_type == PGN_OUT_F32)
+            hipLaunchKernelGGL(seg::segment_write_kernel<float>, grid, dim3(seg::kWriteThreads), 0, s, wa);
+        else
+            hipLaunchKernelGGL(seg::segment_write_kernel<_Float16>, grid, dim3(seg::kWriteThreads), 0, s, wa);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return PGN_OK;
 }
 
 // ---- in-library entry points of the POD5 loader (pgn_internal.h) --------------------------------

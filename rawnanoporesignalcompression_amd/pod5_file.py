@@ -322,6 +322,15 @@ class Pod5File:
         caller.wait_stream(ls)
         return LoadedReads(out, got_off, got_n, status, ReadStats(raw) if raw is not None else None, adc)
 
+    def load_segments(self, codec, reads=None, *, length, overlap, trim=None, dtype=None, **norm_params):
+        """Whole reads of this file as model input: :meth:`load_reads` with ``output="adc"``, then
+        :meth:`PGNanoCodec.segment_reads` over the loaded reads with the loader's per-read status, so a read
+        that failed to decode gives no segments and keeps its status.  reads as in :meth:`load_reads`; the
+        other arguments and the result (:class:`SegmentedReads`) as in ``segment_reads``."""
+        loaded = self.load_reads(codec, reads, output="adc")
+        return codec.segment_reads(loaded.out, loaded.offsets, loaded.counts, length=length, overlap=overlap, trim=trim,
+                                   dtype=dtype, read_status=loaded.status, **norm_params)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.pgn_pod5_file_close(self._h)
