@@ -311,8 +311,7 @@ int pgn_read_stats_device(pgn_ctx *ctx, size_t nreads, const int16_t *d_samples,
  * output and stats of such a read are unspecified.  Nothing is written outside
  * [d_read_out_offsets[r], + n_r) of any read.
  * Not covered: adapter trimming (that is pgn_segment_reads_device, "Trimmed, normalised model segments"
- * below), bfloat16, the host-memory per-chunk calls, a read shared by several workgroups (one workgroup
- * selects one read).  The read -> chunk map of a POD5 file comes from
+ * below), bfloat16, the host-memory per-chunk calls.  The read -> chunk map of a POD5 file comes from
  * pgn_pod5_reads_read, and pgn_pod5_load_reads_device (pgnano_pod5file.h) makes this call from a file. */
 int pgn_decompress_reads_device_norm(pgn_ctx *ctx, int codec, uint32_t max_chunk_samples, size_t nreads,
                                      size_t nchunks, const uint64_t *d_read_first_chunk, const uint8_t *d_in,
@@ -321,6 +320,38 @@ int pgn_decompress_reads_device_norm(pgn_ctx *ctx, int codec, uint32_t max_chunk
                                      const uint64_t *d_read_out_offsets, int16_t *d_adc,
                                      const pgn_norm_params *params, pgn_read_stats *d_stats,
                                      int32_t *d_chunk_status, void *stream);
+
+/* ---- Long reads: one selection shared by several workgroups ---------------------------------------
+ * The statistics above are an exact selection over a read's samples.  A read of up to split_min_samples
+ * is selected by one workgroup (one wave up to 512 samples); a longer one, below 2^32 samples, is selected
+ * in parts = min(ceil(n / part_samples), PGN_SELECT_MAX_PARTS) parts, part j covering samples
+ * [floor(j * n / parts), floor((j + 1) * n / parts)): workgroups histogram the parts, the histograms are
+ * summed per read with integer adds, and the rank walk runs once on the sum.  Every field of
+ * pgn_read_stats, and everything computed from it, is bit for bit what one workgroup gives.
+ * Such a read holds one of max_split_reads slots (a little over 5 KB of context scratch each) for the
+ * call; the slots go to the qualifying reads in read order, and a read that finds none is selected by one
+ * workgroup as before.  The plan lives on the device: the calls keep their arguments, their checks and
+ * their freedom from host waits (context scratch grows with nreads and with max_split_reads, as the
+ * segment call's does).  The setting belongs to the context and is read at each call of
+ * pgn_read_stats_device, pgn_decompress_reads_device_norm, pgn_segment_reads_device and the POD5 loads
+ * built on them.  max_split_reads == 0 switches it off: the launches are then those of one workgroup per
+ * read alone.
+ * Defaults after pgn_ctx_create: split_min_samples 196608, part_samples 32768, max_split_reads 1024.
+ * pgn_ctx_set_select_split returns PGN_ERR_INVALID_ARG for a NULL argument, part_samples outside
+ * [1024, 2^24], split_min_samples < part_samples (so a split read has at least two parts) or
+ * max_split_reads > 65536.
+ * pgn_select_split_counts (a diagnostic) waits for the context's last call and reports its most recent
+ * selection (in pgn_segment_reads_device: the one over the trimmed reads): out[0] reads of one wave,
+ * out[1] reads of one workgroup (those of out[4] included), out[2] split reads, out[3] their parts,
+ * out[4] reads above split_min_samples that found no slot.  All zero when that selection ran with the
+ * split off, or before any. */
+#define PGN_SELECT_MAX_PARTS 4096
+typedef struct pgn_select_split {
+    uint32_t split_min_samples, part_samples, max_split_reads, pad;
+} pgn_select_split;
+int pgn_ctx_set_select_split(pgn_ctx *ctx, const pgn_select_split *s);
+int pgn_ctx_get_select_split(pgn_ctx *ctx, pgn_select_split *s);
+int pgn_select_split_counts(pgn_ctx *ctx, uint64_t out[5]);
 
 /* ---- Per-read calibrated output ------------------------------------------------------------------
  * pgn_decompress_batch_device_pa for whole reads: the chunks are in read order, d_read_first_chunk and
@@ -406,7 +437,7 @@ int pgn_reads_status_device(pgn_ctx *ctx, size_t nreads, const uint64_t *d_read_
  * nreads > 0, a missing array, or nreads >= 2^32.
  * Not covered: a decode-fused entry point (the norm call is decode, then statistics, then a pass, so this
  * call after an int16 decode costs the same); bfloat16; a maximum-trim fraction or a rejection of
- * over-trimmed reads; front padding; one read shared by several workgroups in the selection. */
+ * over-trimmed reads; front padding. */
 typedef struct pgn_trim_params {
     uint32_t max_samples, window, min_elements, min_trim;
     float mad_mult, threshold_mads;

@@ -52,6 +52,15 @@ class ReadStats(C.Structure):
                 ("mad4", C.c_uint32), ("centre", C.c_float), ("spread", C.c_float)]
 
 
+PGN_SELECT_MAX_PARTS = 4096
+
+
+class SelectSplit(C.Structure):
+    """pgn_select_split"""
+    _fields_ = [("split_min_samples", C.c_uint32), ("part_samples", C.c_uint32), ("max_split_reads", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
 class TrimParams(C.Structure):
     """pgn_trim_params"""
     _fields_ = [("max_samples", C.c_uint32), ("window", C.c_uint32), ("min_elements", C.c_uint32),
@@ -126,6 +135,9 @@ SIGNATURES = [
     ("pgn_decompress_reads_device_norm", C.c_int,
      [_VP, C.c_int, C.c_uint32, _SZ, _SZ, _U64P, _VP, _U64P, _U64P, _U32P, _VP, C.c_int, _U64P, _VP, _VP, _VP, _I32P,
       _VP]),
+    ("pgn_ctx_set_select_split", C.c_int, [_VP, C.POINTER(SelectSplit)]),
+    ("pgn_ctx_get_select_split", C.c_int, [_VP, C.POINTER(SelectSplit)]),
+    ("pgn_select_split_counts", C.c_int, [_VP, C.POINTER(C.c_uint64 * 5)]),
     ("pgn_decompress_reads_device_pa", C.c_int,
      [_VP, C.c_int, C.c_uint32, _SZ, _SZ, _U64P, _VP, _U64P, _U64P, _U32P, _VP, C.c_int, _U64P, _VP, _VP, _I32P, _I32P,
       _VP]),

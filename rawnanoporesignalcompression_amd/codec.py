@@ -254,6 +254,19 @@ def trim_signal(adc, **trim) -> int:
     return T.min_trim
 
 
+def select_parts(n: int, split_min_samples: int, part_samples: int):
+    """The plan of one read's selection on the host (include/pgnano_hip.h, "Long reads"): the boundaries of
+    the parts a read of ``n`` samples is selected in under :meth:`PGNanoCodec.set_select_split`'s settings, as
+    ``parts + 1`` ascending uint64 values from 0 to ``n``.  A read that is not split has one part."""
+    n, split_min_samples, part_samples = int(n), int(split_min_samples), int(part_samples)
+    if not (1024 <= part_samples <= 1 << 24 and part_samples <= split_min_samples < 1 << 32) or n < 0:
+        raise ValueError("need 1024 <= part_samples <= 2**24 and part_samples <= split_min_samples < 2**32")
+    parts = 1
+    if split_min_samples < n < 1 << 32:
+        parts = min(-(-n // part_samples), _native.PGN_SELECT_MAX_PARTS)
+    return np.array([j * n // parts for j in range(parts + 1)], dtype=np.uint64)
+
+
 def _host_stats(y, prm):
     """(centre, spread) of one read on the host, as the per-read normalisation section defines them."""
     f32 = np.float32
@@ -375,6 +388,33 @@ class PGNanoCodec:
     @property
     def stream(self) -> int:
         return int(self._lib.pgn_ctx_stream(self._h) or 0)
+
+    # ---- long reads: the selection shared by several workgroups ---------------------------
+    @property
+    def select_split(self):
+        """``(split_min_samples, part_samples, max_split_reads)`` of this context (pgn_ctx_get_select_split):
+        a read above ``split_min_samples`` is selected in parts of about ``part_samples`` by several workgroups,
+        at most ``max_split_reads`` reads per call (0: off).  The statistics do not depend on it."""
+        s = _native.SelectSplit()
+        _check(self._lib.pgn_ctx_get_select_split(self._h, C.byref(s)))
+        return int(s.split_min_samples), int(s.part_samples), int(s.max_split_reads)
+
+    def set_select_split(self, split_min_samples=None, part_samples=None, max_split_reads=None) -> None:
+        """Change the settings of :attr:`select_split`; an argument left out keeps its value."""
+        cur = self.select_split
+        new = [cur[i] if v is None else int(v) for i, v in enumerate((split_min_samples, part_samples, max_split_reads))]
+        if any(not 0 <= v < 1 << 32 for v in new):
+            raise ValueError("the select_split settings are uint32")
+        _check(self._lib.pgn_ctx_set_select_split(self._h, C.byref(_native.SelectSplit(*new, 0))))
+
+    def select_split_counts(self) -> dict:
+        """How the most recent selection of this context treated its reads (pgn_select_split_counts; waits for
+        the context's last call): reads of one wave (``short``), of one workgroup (``whole``), ``split`` reads
+        and their ``parts``, and the reads among ``whole`` that were long enough but found ``no_slot``.  All 0
+        when the split is off."""
+        out = (C.c_uint64 * 5)()
+        _check(self._lib.pgn_select_split_counts(self._h, C.byref(out)))
+        return dict(zip(("short", "whole", "split", "parts", "no_slot"), (int(v) for v in out)))
 
     # ---- per-chunk plugin surface (host memory) -------------------------------------------
     def compress_signal(self, samples, read_data=None, is_last_batch: bool = False) -> bytes:

@@ -145,6 +145,19 @@ int pgnm_locate(const uint32_t* coarse, const uint32_t* k, int nranks, uint32_t*
     return 0;
 }
 
+// The plan of a long read's selection (pgn_select.h split_parts / part_begin): *parts of them, and the
+// first min(*parts + 1, max) part boundaries (begin[j] is where part j starts; begin[*parts] == n).
+// Returns 0, or -1 for settings pgn_ctx_set_select_split rejects.
+int pgnm_select_parts(uint64_t n, uint32_t split_min_samples, uint32_t part_samples, uint32_t* parts, uint64_t max,
+                      uint64_t* begin)
+{
+    const pgn_select_split s{split_min_samples, part_samples, 0, 0};
+    if (!pgn::sel::split_valid(&s) || !parts) return -1;
+    *parts = pgn::sel::split_parts(n, split_min_samples, part_samples);
+    for (uint64_t j = 0; j <= *parts && j < max; j++) begin[j] = pgn::sel::part_begin(n, *parts, (uint32_t)j);
+    return 0;
+}
+
 // The head trim (pgn_segment.h) of one read: the selection above over the head, the threshold and the
 // window scan as the header writes it.  Returns 0, or -1 for parameters the C ABI rejects.
 int pgnm_trim(const int16_t* x, uint64_t n, const pgn_trim_params* prm, uint32_t* trim, int32_t* head_m2,

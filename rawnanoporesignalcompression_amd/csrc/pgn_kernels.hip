@@ -2130,6 +2130,15 @@ struct pgn_ctx {
     // trimmed read's statistics; then the segment total (one block, carved up by ensure_segment)
     uint8_t* segWork = nullptr;
     size_t segReads = 0;
+    // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
+    // first work items and the slots in one block sized by max_split_reads; the per-read counts the one-workgroup kernel reads.
+    // Defaults measured by tools/select_split_timing.py (profiles/select_split_timing.log)
+    pgn_select_split split = {196608u, 32768u, 1024u, 0u};
+    uint8_t* splitWork = nullptr;
+    size_t splitSlots = 0;
+    uint64_t* splitWholeCounts = nullptr;
+    size_t splitReads = 0;
+    bool splitCounted = false;  // the last selection ran the plan kernel (pgn_select_split_counts)
     // an object of another translation unit (the POD5 loader's staging, pgn_internal.h)
     void* ext = nullptr;
     void (*extDestroy)(void*) = nullptr;
@@ -2320,6 +2329,8 @@ int pgn_ctx_destroy(pgn_ctx* c)
     (void)hipFree(c->normReadN);
     (void)hipFree(c->normStats);
     (void)hipFree(c->segWork);
+    (void)hipFree(c->splitWork);
+    (void)hipFree(c->splitWholeCounts);
     if (c->largeHdrHost) (void)hipHostFree(c->largeHdrHost);
     for (hipEvent_t e : {c->evScanFork, c->evScan})
         if (e) (void)hipEventDestroy(e);
@@ -3320,16 +3331,118 @@ static int ensure_norm(pgn_ctx* c, size_t nreads, size_t nchunks)
     return PGN_OK;
 }
 
-// the two statistics kernels: reads above sel::kShortMax samples one workgroup each, the others one wave each
-static int launch_read_stats(pgn_ctx* c, const sel::StatsArgs& a, hipStream_t s)
+// scratch of the split selection: [SplitHead][itemFirst: slots + 1][slots], and per read the counts of
+// the one-workgroup kernel, followed by the classify blocks' totals (one per 512 reads)
+static int ensure_split(pgn_ctx* c, size_t nreads, sel::SplitArgs& sa)
+{
+    const size_t slots = c->split.max_split_reads;
+    const auto firstBytes = [](size_t n) { return ((n + 1) * sizeof(uint32_t) + 63) & ~(size_t)63; };
+    if (slots > c->splitSlots) {
+        wait_last_host(c);
+        (void)hipFree(c->splitWork);
+        c->splitWork = nullptr;
+        c->splitSlots = 0;
+        HIPCHK(hipMalloc(&c->splitWork, 64 + firstBytes(slots) + slots * sizeof(sel::SplitSlot)));
+        c->splitSlots = slots;
+    }
+    if (nreads > c->splitReads) {
+        wait_last_host(c);
+        (void)hipFree(c->splitWholeCounts);
+        c->splitWholeCounts = nullptr;
+        c->splitReads = 0;
+        const size_t nblocks = (nreads + sel::kPlanThreads - 1) / sel::kPlanThreads;
+        HIPCHK(hipMalloc(&c->splitWholeCounts, nreads * sizeof(uint64_t) + nblocks * sizeof(sel::SplitBlock)));
+        c->splitReads = nreads;
+    }
+    static_assert(sizeof(sel::SplitHead) <= 64, "the head's room");
+    sa.head = reinterpret_cast<sel::SplitHead*>(c->splitWork);
+    sa.itemFirst = reinterpret_cast<uint32_t*>(c->splitWork + 64);
+    sa.slots = reinterpret_cast<sel::SplitSlot*>(c->splitWork + 64 + firstBytes(c->splitSlots));
+    sa.wholeCounts = c->splitWholeCounts;
+    sa.blocks = reinterpret_cast<sel::SplitBlock*>(c->splitWholeCounts + c->splitReads);
+    return PGN_OK;
+}
+
+// The statistics kernels: reads above sel::kShortMax samples one workgroup each, the others one wave
+// each; with the split on, the classification and the plan first, and after them the kernels that select
+// the reads holding a slot in parts.  countBound: what the host knows no read's count exceeds; where that
+// rules a split out, the launches are those without it.
+static int launch_read_stats(pgn_ctx* c, sel::StatsArgs a, hipStream_t s, uint64_t countBound = ~0ull)
 {
     const size_t cus = (size_t)(c->numCUs > 0 ? c->numCUs : 1);
+    const bool split = c->split.max_split_reads > 0 && countBound > c->split.split_min_samples;
+    sel::SplitArgs sa{};
+    c->splitCounted = false;
+    if (split) {
+        const int rc = ensure_split(c, a.nreads, sa);
+        if (rc != PGN_OK) return rc;
+        sa.splitMin = c->split.split_min_samples;
+        sa.partSamples = c->split.part_samples;
+        sa.maxSlots = c->split.max_split_reads;
+        sa.a = a;
+        const size_t nblocks = (a.nreads + sel::kPlanThreads - 1) / sel::kPlanThreads;
+        hipLaunchKernelGGL(sel::split_classify_kernel, dim3((unsigned)nblocks), dim3(sel::kPlanThreads), 0, s, sa);
+        hipLaunchKernelGGL(sel::split_plan_kernel, dim3(1), dim3(sel::kPlanThreads), 0, s, sa);
+        HIPCHK(hipGetLastError());
+        c->splitCounted = true;
+    }
+    // the one-workgroup kernel is the same code either way: with the split on it reads the plan's counts,
+    // in which a read that holds a slot has none
+    sel::StatsArgs whole = a;
+    if (split) whole.counts = sa.wholeCounts;
     const size_t longGrid = std::min<size_t>(a.nreads, cus * 4);
-    hipLaunchKernelGGL(sel::read_stats_kernel, dim3((unsigned)longGrid), dim3(sel::kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(sel::read_stats_kernel, dim3((unsigned)longGrid), dim3(sel::kSelThreads), 0, s, whole);
     HIPCHK(hipGetLastError());
     const size_t shortGrid = std::min<size_t>((a.nreads + 3) / 4, cus * 8);
     hipLaunchKernelGGL(sel::read_stats_short_kernel, dim3((unsigned)shortGrid), dim3(sel::kSelThreads), 0, s, a);
     HIPCHK(hipGetLastError());
+    if (split) {
+        // fixed grids (the host knows neither the slots in use nor their parts): the parts kernels hold
+        // 32 KB of LDS per workgroup, the slot kernels are one wave per slot
+        const dim3 partsGrid((unsigned)(cus * 4)), threads(sel::kSelThreads);
+        const dim3 slotGrid((unsigned)std::min<size_t>(sa.maxSlots, cus * 8)), wave(sel::kSlotThreads);
+        hipLaunchKernelGGL((sel::split_parts_kernel<false, false>), partsGrid, threads, 0, s, sa);
+        hipLaunchKernelGGL(sel::split_place_kernel, slotGrid, wave, 0, s, sa, 0u);
+        hipLaunchKernelGGL((sel::split_parts_kernel<false, true>), partsGrid, threads, 0, s, sa);
+        hipLaunchKernelGGL(sel::split_finish_kernel<false>, slotGrid, wave, 0, s, sa);
+        HIPCHK(hipGetLastError());
+        if (a.prm.mode == PGN_NORM_MEDMAD) {
+            hipLaunchKernelGGL((sel::split_parts_kernel<true, false>), partsGrid, threads, 0, s, sa);
+            hipLaunchKernelGGL(sel::split_place_kernel, slotGrid, wave, 0, s, sa, 1u);
+            hipLaunchKernelGGL((sel::split_parts_kernel<true, true>), partsGrid, threads, 0, s, sa);
+            hipLaunchKernelGGL(sel::split_finish_kernel<true>, slotGrid, wave, 0, s, sa);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return PGN_OK;
+}
+
+extern "C" int pgn_ctx_set_select_split(pgn_ctx* c, const pgn_select_split* v)
+{
+    if (!c || !sel::split_valid(v)) return PGN_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->split = *v;
+    c->split.pad = 0;
+    return PGN_OK;
+}
+
+extern "C" int pgn_ctx_get_select_split(pgn_ctx* c, pgn_select_split* v)
+{
+    if (!c || !v) return PGN_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    *v = c->split;
+    return PGN_OK;
+}
+
+extern "C" int pgn_select_split_counts(pgn_ctx* c, uint64_t out[5])
+{
+    if (!c || !out) return PGN_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    wait_last_host(c);
+    for (int i = 0; i < 5; i++) out[i] = 0;
+    if (c->splitCounted)
+        HIPCHK(hipMemcpy(out, c->splitWork + offsetof(sel::SplitHead, counts), 5 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PGN_OK;
 }
 
@@ -3560,7 +3673,7 @@ extern "C" int pgn_segment_reads_device(pgn_ctx* c, size_t nreads, const int16_t
         // med/MAD of the heads: only m2 and mad4 are used, so the float parameters are placeholders
         const pgn_norm_params headPrm{PGN_NORM_MEDMAD, 0, 0.0, 1.0, 1.0f, 1.0f, 1.0f, 0.0f};
         const sel::StatsArgs ha{d_samples, d_read_offsets, w.headN, nreads, headPrm, w.headStats, nullptr, nullptr};
-        rc = launch_read_stats(c, ha, s);
+        rc = launch_read_stats(c, ha, s, trim->max_samples);  // a head has at most max_samples
         if (rc != PGN_OK) return rc;
         hipLaunchKernelGGL(seg::trim_kernel, dim3(waveGrid), dim3(256), 0, s, ta);
         HIPCHK(hipGetLastError());

@@ -144,6 +144,28 @@ inline bool params_valid(const pgn_norm_params* P)
     return P->spread_floor > 0.0f;
 }
 
+// ---- one read shared by several workgroups: the plan (include/pgnano_hip.h pgn_select_split) -----
+// The parts a read of n samples is selected in: 1 (not split) up to split_min_samples and from 2^32 on,
+// else ceil(n / part_samples) capped at PGN_SELECT_MAX_PARTS.  split_min_samples >= part_samples, so a
+// split read has at least two parts.
+PGN_HD uint32_t split_parts(uint64_t n, uint32_t splitMin, uint32_t partSamples)
+{
+    if (n <= splitMin || (n >> 32)) return 1;
+    const uint64_t p = (n + partSamples - 1) / partSamples;
+    return p < PGN_SELECT_MAX_PARTS ? (uint32_t)p : (uint32_t)PGN_SELECT_MAX_PARTS;
+}
+// Part j of `parts` covers [part_begin(j), part_begin(j + 1)): the parts tile [0, n) and, with
+// parts <= n, none is empty (n < 2^32 and j <= 4096, so the product fits 64 bits).
+PGN_HD uint64_t part_begin(uint64_t n, uint32_t parts, uint32_t j) { return (uint64_t)j * n / parts; }
+
+// PGN_ERR_INVALID_ARG conditions of pgn_ctx_set_select_split
+inline bool split_valid(const pgn_select_split* s)
+{
+    if (!s) return false;
+    if (s->part_samples < 1024u || s->part_samples > (1u << 24)) return false;
+    return s->split_min_samples >= s->part_samples && s->max_split_reads <= 65536u;
+}
+
 // ---- the selection on the host, over serially built histograms (libpgn_model.so) ---------------
 template <bool MAD>
 inline void host_select2(const int16_t* x, uint64_t n, int32_t m2, uint32_t kLo, uint32_t kHi, uint32_t& vLo, uint32_t& vHi)
@@ -400,6 +422,302 @@ __global__ __launch_bounds__(kSelThreads) void read_stats_short_kernel(StatsArgs
             s.status = read_status(a, r);
             a.stats[r] = s;
         }
+    }
+}
+
+// ---- one read shared by several workgroups ------------------------------------------------------------
+// A read above split_min_samples takes a slot (while there are slots) and is selected in parts: every
+// part's histogram is added to the slot's with integer atomics, and the rank walk and the refinement run
+// once per slot on the sums.  The order on the stream is classify -> plan -> (the kernels above) ->
+// coarse parts -> place -> fine parts -> finish (med/MAD: the last four again with MAD keys); every
+// dependency is a kernel boundary, and no workgroup waits for another inside a kernel.
+struct SplitSlot {
+    alignas(16) uint32_t coarse[kCoarseBins];  // the parts' coarse histograms, summed
+    uint32_t fine[2 * kMaxFineBins];           // the two fine histograms, the second at 1 << shift
+    Place place[2];
+    uint64_t read;
+    int32_t m2;
+    uint32_t pad;
+};
+static_assert(sizeof(SplitSlot) % 16 == 0 && offsetof(SplitSlot, fine) == sizeof(uint32_t) * kCoarseBins, "slot layout");
+constexpr uint32_t kSlotHistVecs = (kCoarseBins + 2 * kMaxFineBins) / 4;  // the histograms as 16-byte words
+
+struct SplitHead {
+    uint32_t nslots, nitems;  // slots handed out, and their parts: the work items of the parts kernels
+    uint64_t counts[5];       // pgn_select_split_counts
+};
+
+struct SplitBlock {         // what the plan needs of 512 consecutive reads
+    uint32_t qual, nshort;  // reads above split_min_samples and below 2^32; reads of at most kShortMax samples
+    uint64_t parts;         // the parts of the former
+};
+
+struct SplitArgs {
+    StatsArgs a;
+    uint32_t splitMin, partSamples, maxSlots, pad;
+    uint64_t* wholeCounts;  // out (plan): per read, its count as read_stats_kernel is to see it -- 0 (a read
+                            // it skips) where the read holds a slot
+    SplitBlock* blocks;     // out (classify): one per 512 reads
+    SplitHead* head;
+    uint32_t* itemFirst;    // maxSlots + 1: the first work item of every slot, then their count
+    SplitSlot* slots;
+};
+
+// the reads of one classify block and the plan's workgroup: 512 threads leave the plan 256 registers a
+// thread, which it needs to stay out of scratch
+constexpr uint32_t kPlanThreads = 512;
+
+// Classification, across the device: one block per 512 consecutive reads writes the block's totals
+// and copies the reads' counts for the one-workgroup kernel (the plan zeroes those of the reads it
+// gives slots).
+__global__ __launch_bounds__(kPlanThreads) void split_classify_kernel(SplitArgs s)
+{
+    __shared__ unsigned long long tot[3];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 3) tot[tid] = 0;
+    __syncthreads();
+    const uint64_t r = (uint64_t)blockIdx.x * kPlanThreads + tid;
+    const bool valid = r < s.a.nreads;
+    const uint64_t n = valid ? s.a.counts[r] : 0;
+    if (valid) s.wholeCounts[r] = n;
+    const uint32_t parts = split_parts(n, s.splitMin, s.partSamples);
+    const uint64_t qual = __ballot(parts > 1), small = __ballot(valid && n <= kShortMax);
+    if ((tid & 63u) == 0) {
+        if (qual) atomicAdd(&tot[0], (unsigned long long)__popcll(qual));
+        if (small) atomicAdd(&tot[1], (unsigned long long)__popcll(small));
+    }
+    if (parts > 1) atomicAdd(&tot[2], (unsigned long long)parts);
+    __syncthreads();
+    if (tid == 0) {
+        SplitBlock b;
+        b.qual = (uint32_t)tot[0];
+        b.nshort = (uint32_t)tot[1];
+        b.parts = tot[2];
+        s.blocks[blockIdx.x] = b;
+    }
+}
+
+// Exclusive scan of (q, p) over the plan's workgroup (shuffles inside a wave, the 16 wave totals through
+// LDS), with the totals.
+__device__ __forceinline__ void plan_scan(uint32_t q, uint64_t p, uint32_t* waveQual, uint64_t* waveParts, uint64_t& exQ,
+                                          uint64_t& exP, uint64_t& allQ, uint64_t& allP)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inclQ = q;
+    uint64_t inclP = p;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t upQ = __shfl_up(inclQ, d);
+        const uint64_t upP = __shfl_up(inclP, d);
+        if (lane >= d) {
+            inclQ += upQ;
+            inclP += upP;
+        }
+    }
+    if (lane == 63) {
+        waveQual[wave] = inclQ;
+        waveParts[wave] = inclP;
+    }
+    __syncthreads();
+    uint64_t beforeQ = 0, beforeP = 0;
+    allQ = allP = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kPlanThreads / 64; i++) {
+        const uint64_t wq = waveQual[i], wp = waveParts[i];
+        beforeQ += i < wave ? wq : 0;
+        beforeP += i < wave ? wp : 0;
+        allQ += wq;
+        allP += wp;
+    }
+    exQ = beforeQ + inclQ - q;
+    exP = beforeP + inclP - p;
+    __syncthreads();  // the next scan writes the wave totals
+}
+
+// The plan, by one workgroup (pgn_segment.h's count-and-scan, over the classify blocks' totals, 512
+// blocks per step): the slots go out in read order and the work items (slot, part) are numbered; only a
+// block that holds a read above split_min_samples is looked at read by read.  Then the counters, and the
+// histograms of the slots used are cleared.
+__global__ __launch_bounds__(kPlanThreads) void split_plan_kernel(SplitArgs s)
+{
+    __shared__ uint64_t waveParts[kPlanThreads / 64];
+    __shared__ uint32_t waveQual[kPlanThreads / 64];
+    __shared__ uint32_t blkQual[kPlanThreads];
+    __shared__ uint64_t blkSlot[kPlanThreads], blkItem[kPlanThreads];  // a block's first slot and work item
+    __shared__ unsigned long long cnt[2];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 2) cnt[tid] = 0;
+    const uint64_t nblocks = (s.a.nreads + kPlanThreads - 1) / kPlanThreads;
+    uint64_t carryQ = 0, carryP = 0;  // qualifying reads and their parts so far
+    uint64_t nShort = 0;
+    uint32_t nParts = 0;
+    for (uint64_t bbase = 0; bbase < nblocks; bbase += kPlanThreads) {
+        SplitBlock info{0, 0, 0};
+        if (bbase + tid < nblocks) info = s.blocks[bbase + tid];
+        uint64_t exQ, exP, allQ, allP;
+        plan_scan(info.qual, info.parts, waveQual, waveParts, exQ, exP, allQ, allP);
+        blkQual[tid] = info.qual;
+        blkSlot[tid] = carryQ + exQ;
+        blkItem[tid] = carryP + exP;
+        nShort += info.nshort;
+        __syncthreads();
+        const uint32_t nb = nblocks - bbase < kPlanThreads ? (uint32_t)(nblocks - bbase) : kPlanThreads;
+        for (uint32_t i = 0; i < nb; i++) {
+            // the reads that qualify before a read all hold slots while slot < maxSlots, so their parts
+            // are the work items before that read's; the read with slot == maxSlots marks their end
+            if (blkQual[i] == 0 || blkSlot[i] > s.maxSlots) continue;
+            const uint64_t r = (bbase + i) * kPlanThreads + tid;
+            const uint64_t n = r < s.a.nreads ? s.a.counts[r] : 0;
+            const uint32_t parts = split_parts(n, s.splitMin, s.partSamples);
+            const uint32_t q = parts > 1 ? 1u : 0u;
+            uint64_t inQ, inP, blockQ, blockP;
+            plan_scan(q, q ? parts : 0u, waveQual, waveParts, inQ, inP, blockQ, blockP);
+            const uint64_t slot = blkSlot[i] + inQ, item = blkItem[i] + inP;
+            if (q && slot < s.maxSlots) {
+                s.wholeCounts[r] = 0;
+                s.itemFirst[slot] = (uint32_t)item;
+                s.slots[slot].read = r;
+                nParts += parts;
+            } else if (q && slot == s.maxSlots) {
+                s.itemFirst[slot] = (uint32_t)item;
+            }
+        }
+        carryQ += allQ;
+        carryP += allP;
+        __syncthreads();  // the next step writes the blocks' arrays
+    }
+    atomicAdd(&cnt[0], (unsigned long long)nShort);
+    atomicAdd(&cnt[1], (unsigned long long)nParts);
+    __syncthreads();
+    const uint32_t nslots = carryQ < s.maxSlots ? (uint32_t)carryQ : s.maxSlots;
+    if (tid == 0) {
+        if (carryQ <= s.maxSlots) s.itemFirst[carryQ] = (uint32_t)carryP;
+        s.head->nslots = nslots;
+        s.head->nitems = (uint32_t)cnt[1];
+        s.head->counts[0] = cnt[0];
+        s.head->counts[1] = s.a.nreads - cnt[0] - nslots;
+        s.head->counts[2] = nslots;
+        s.head->counts[3] = cnt[1];
+        s.head->counts[4] = carryQ - nslots;
+    }
+    for (uint64_t i = tid; i < (uint64_t)nslots * kSlotHistVecs; i += kPlanThreads)
+        reinterpret_cast<uint4*>(s.slots + i / kSlotHistVecs)[i % kSlotHistVecs] = make_uint4(0, 0, 0, 0);
+}
+
+// The histogram of one part of a split read, added to its slot's: pass 1 (FINE false) counts the keys'
+// coarse bins, pass 2 the low bits of the keys in the two placed bins, as select2 does for a whole read.
+// A fixed grid loops over the work items; item -> slot by bisection of itemFirst.
+template <bool MAD, bool FINE>
+__global__ __launch_bounds__(kSelThreads) void split_parts_kernel(SplitArgs s)
+{
+    constexpr uint32_t shift = MAD ? kMadShift : kPlainShift, fineBins = 1u << shift;
+    constexpr uint32_t bins = FINE ? 2 * fineBins : kCoarseBins;
+    __shared__ alignas(16) uint32_t hist[bins * kCopies];  // [bin][copy]
+    const uint32_t tid = threadIdx.x, copy = tid & (kCopies - 1);
+    const uint32_t nitems = s.head->nitems, nslots = s.head->nslots;
+    uint4* h4 = reinterpret_cast<uint4*>(hist);
+    for (uint32_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+        uint32_t lo = 0, hi = nslots;  // itemFirst[lo] <= item < itemFirst[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s.itemFirst[mid] <= item) lo = mid;
+            else hi = mid;
+        }
+        SplitSlot& S = s.slots[lo];
+        const uint32_t first = s.itemFirst[lo], parts = s.itemFirst[lo + 1] - first, j = item - first;
+        const uint64_t r = S.read, n = s.a.counts[r];
+        const uint64_t b0 = part_begin(n, parts, j), b1 = part_begin(n, parts, j + 1);
+        const int16_t* p = s.a.samples + s.a.offsets[r] + b0;
+        const int32_t m2 = MAD ? S.m2 : 0;
+        for (uint32_t i = tid; i < bins * kCopies / 4; i += kSelThreads) h4[i] = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        if constexpr (FINE) {
+            const uint32_t bLo = S.place[0].bin, bHi = S.place[1].bin;
+            scan_keys<MAD>(p, (uint32_t)(b1 - b0), m2, [&](uint32_t key) {
+                const uint32_t b = key >> shift, f = key & (fineBins - 1);
+                if (b == bLo) atomicAdd(&hist[f * kCopies + copy], 1u);
+                else if (b == bHi) atomicAdd(&hist[(fineBins + f) * kCopies + copy], 1u);
+            });
+        } else {
+            scan_keys<MAD>(p, (uint32_t)(b1 - b0), m2,
+                           [&](uint32_t key) { atomicAdd(&hist[(key >> shift) * kCopies + copy], 1u); });
+        }
+        __syncthreads();
+        uint32_t* dst = FINE ? S.fine : S.coarse;
+        for (uint32_t b = tid; b < bins; b += kSelThreads) {
+            const uint4 u = h4[b * 2], v = h4[b * 2 + 1];
+            const uint32_t sum = u.x + u.y + u.z + u.w + v.x + v.y + v.z + v.w;
+            if (sum) atomicAdd(&dst[b], sum);
+        }
+        __syncthreads();  // the next item clears what this one read
+    }
+}
+
+constexpr uint32_t kSlotThreads = 64;  // the place and finish kernels: one wave per slot
+
+// The ranks of a slot's read in its summed coarse histogram: what thread 0 of select2 does.  `mad`: the
+// second selection of med/MAD (the same ranks, MAD keys).
+__global__ __launch_bounds__(kSlotThreads) void split_place_kernel(SplitArgs s, uint32_t mad)
+{
+    __shared__ alignas(16) uint32_t coarse[kCoarseBins];
+    __shared__ uint32_t groups[kGroups];
+    const uint32_t lane = threadIdx.x, nslots = s.head->nslots;
+    for (uint32_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
+        SplitSlot& S = s.slots[slot];
+        const uint32_t n = (uint32_t)s.a.counts[S.read];
+        const uint4* c4 = reinterpret_cast<const uint4*>(S.coarse);
+#pragma unroll
+        for (uint32_t j = 0; j < kGroups / kSlotThreads; j++) {  // a 16-byte word is one group
+            const uint4 v = c4[j * kSlotThreads + lane];
+            reinterpret_cast<uint4*>(coarse)[j * kSlotThreads + lane] = v;
+            groups[j * kSlotThreads + lane] = v.x + v.y + v.z + v.w;
+        }
+        __syncthreads();
+        if (lane == 0) {
+            const bool quantile = !mad && s.a.prm.mode == PGN_NORM_QUANTILE;
+            const uint32_t k[2] = {quantile ? rank_of(s.a.prm.p_lo, n) : (n - 1) / 2,
+                                   quantile ? rank_of(s.a.prm.p_hi, n) : n / 2};
+            Place pl[2];
+            locate<2>(groups, coarse, k, pl);
+            S.place[0] = pl[0];
+            S.place[1] = pl[1];
+        }
+        __syncthreads();  // the next slot overwrites the histogram
+    }
+}
+
+// The two values from a slot's fine histograms, then the read's statistics -- or, after the median's
+// selection of med/MAD, m2 and histograms cleared for the selection with MAD keys.
+template <bool MAD>
+__global__ __launch_bounds__(kSlotThreads) void split_finish_kernel(SplitArgs s)
+{
+    constexpr uint32_t shift = MAD ? kMadShift : kPlainShift, fineBins = 1u << shift;
+    __shared__ alignas(16) uint32_t fine[2 * kMaxFineBins];
+    __shared__ uint32_t val[2];
+    const uint32_t lane = threadIdx.x, nslots = s.head->nslots;
+    for (uint32_t slot = blockIdx.x; slot < nslots; slot += gridDim.x) {
+        SplitSlot& S = s.slots[slot];
+        reinterpret_cast<uint4*>(fine)[lane] = reinterpret_cast<const uint4*>(S.fine)[lane];
+        __syncthreads();
+        if (lane < 2) {
+            const Place pl = S.place[lane];
+            val[lane] = refine(pl, fine + ((lane == 1 && S.place[1].bin != S.place[0].bin) ? fineBins : 0), shift);
+        }
+        __syncthreads();
+        const uint32_t lo = val[0], hi = val[1];
+        if (!MAD && s.a.prm.mode == PGN_NORM_MEDMAD) {
+            if (lane == 0) S.m2 = unkey_plain(lo) + unkey_plain(hi);
+            for (uint32_t i = lane; i < kSlotHistVecs; i += kSlotThreads)
+                reinterpret_cast<uint4*>(&S)[i] = make_uint4(0, 0, 0, 0);
+        } else if (lane == 0) {
+            const uint64_t r = S.read;
+            pgn_read_stats st;
+            stats_clear(st, s.a.counts[r], read_status(s.a, r));
+            if (MAD) finish_medmad(s.a.prm, S.m2, lo + hi, st);
+            else finish_quantile(s.a.prm, unkey_plain(lo), unkey_plain(hi), st);
+            s.a.stats[r] = st;
+        }
+        __syncthreads();  // the next slot overwrites fine and val
     }
 }
 
