@@ -45,6 +45,122 @@ size_t z1m_sequences(const uint8_t* src, size_t n, uint32_t* out3, size_t maxSeq
     return nb;
 }
 
+// Search profile of a single-block frame (n <= 128 KiB): fast_search_serial restated with the
+// bookkeeping that says which of the wave search's paths (pgn_zenc.h fast_search_wave) a sequence
+// takes there.  Visits are numbered from the last match (k) and grouped in 64s, as the wave's rounds
+// are.  One row of kProfileCols words per sequence:
+//   0 position of the match (after the backward extension)      1 k (0 for a post-match repcode)
+//   2 kind: 0 repcode at ip0 + 2, 1 table candidate, 2 candidate written by an earlier visit of the
+//     same group of 64, 3 post-match repcode                     3 backward extension
+//   4 match length    5 1 when the match ran to the stream's end
+//   6 lookups of the group, at or before the hit, whose table candidate (not one of the group's own
+//     writes) had the entry's fingerprint (pgn_zenc.h ht_fp at ht_idx_bits(n)) but other 4 bytes
+//   7 litLength   8 offset value   9 matchLength - 3   (z1m_sequences' triple)
+// Returns the number of sequences; writes the first max_rows rows.
+static const size_t kProfileCols = 10;
+size_t z1m_search_profile(const uint8_t* src, size_t n, uint32_t* rows, size_t max_rows)
+{
+    if (n < 7 || n > kMaxSrc) return 0;
+    const Params p = level1_params(n);
+    const unsigned hlog = p.hashLog, mls = p.mls;
+    const uint32_t idxBits = (n + 2 < (1u << 17)) ? 17u : 20u;
+    auto fp = [&](uint32_t bytes) { return (bytes * 0x9E3779B1u) >> (32u - (27u - idxBits)); };
+    uint32_t* ht = (uint32_t*)calloc((size_t)1 << 15, 4);
+    uint32_t* wr = (uint32_t*)calloc((size_t)1 << 15, 4);  // who wrote the entry: (segment << 5 | group) + 1, 0 after a match
+    size_t nbSeq = 0;
+    auto row = [&](long pos, uint32_t k, uint32_t kind, uint32_t back, size_t ml, bool toEnd, uint32_t nfalse, long ll,
+                   uint32_t offset) {
+        if (nbSeq < max_rows) {
+            uint32_t* r = rows + kProfileCols * nbSeq;
+            r[0] = (uint32_t)pos; r[1] = k; r[2] = kind; r[3] = back; r[4] = (uint32_t)ml; r[5] = toEnd ? 1u : 0u;
+            r[6] = nfalse; r[7] = (uint32_t)ll; r[8] = offset; r[9] = (uint32_t)(ml - 3);
+        }
+        nbSeq++;
+    };
+    long ip0 = 1, ip1 = 2, anchor = 0;
+    const long iend = (long)n, ilimit = (long)n - 8;
+    const uint32_t lowIdx = 1;
+    uint32_t offset_1 = 1, offset_2 = 0;  // offset_2 (4) lies beyond the first position: invalidated
+    uint32_t segment = 0, k = 0, nfalse = 0;
+    while (ip1 < ilimit) {
+        const long ip2 = ip0 + 2;
+        if (k % 64 == 0) nfalse = 0;
+        const uint32_t me = ((segment << 5) | (k / 64)) + 1;  // k / 64 < 21: a block's chain has under 1344 visits
+        const uint32_t h0 = hash_at(src + ip0, hlog, mls), h1 = hash_at(src + ip1, hlog, mls);
+        const uint32_t val0 = rd32(src + ip0), val1 = rd32(src + ip1);
+        const uint32_t cur0 = (uint32_t)ip0 + 1, cur1 = (uint32_t)ip1 + 1;
+        const uint32_t mi0 = ht[h0], mi1 = ht[h1];
+        const bool own0 = wr[h0] == me, own1 = wr[h1] == me;
+        ht[h0] = cur0; wr[h0] = me;
+        ht[h1] = cur1; wr[h1] = me;
+        long match0;
+        size_t mLength;
+        uint32_t offcode, kind, back = 0;
+        if ((offset_1 > 0) && (rd32(src + ip2 - offset_1) == rd32(src + ip2))) {
+            mLength = (src[ip2 - 1] == src[ip2 - (long)offset_1 - 1]) ? 1 : 0;
+            ip0 = ip2 - (long)mLength;
+            match0 = ip0 - (long)offset_1;
+            mLength += 4;
+            offcode = 0;
+            kind = 0;
+        } else {
+            const bool eq0 = (mi0 > lowIdx) && rd32(src + mi0 - 1) == val0;
+            const bool eq1 = (mi1 > lowIdx) && rd32(src + mi1 - 1) == val1;
+            if ((mi0 > lowIdx) && !eq0 && !own0 && fp(rd32(src + mi0 - 1)) == fp(val0)) nfalse++;
+            if (!eq0 && (mi1 > lowIdx) && !eq1 && !own1 && fp(rd32(src + mi1 - 1)) == fp(val1)) nfalse++;
+            if (eq0) {
+                match0 = (long)mi0 - 1;
+                kind = own0 ? 2 : 1;
+            } else if (eq1) {
+                ip0 = ip1;
+                match0 = (long)mi1 - 1;
+                kind = own1 ? 2 : 1;
+            } else {
+                const long step = ((ip0 - anchor) >> 7) + 2;
+                ip0 += step;
+                ip1 += step;
+                k++;
+                continue;
+            }
+            offset_2 = offset_1;
+            offset_1 = (uint32_t)(ip0 - match0);
+            offcode = offset_1 + 2;
+            mLength = 4;
+            while ((ip0 > anchor) && (match0 > 0) && (src[ip0 - 1] == src[match0 - 1])) {
+                ip0--;
+                match0--;
+                mLength++;
+                back++;
+            }
+        }
+        mLength += match_count(src, (size_t)ip0 + mLength, (size_t)match0 + mLength, (size_t)iend);
+        row(ip0, k, kind, back, mLength, ip0 + (long)mLength == iend, nfalse, ip0 - anchor, offcode + 1);
+        ip0 += (long)mLength;
+        anchor = ip0;
+        if (ip0 <= ilimit) {
+            const uint32_t ha = hash_at(src + cur0 + 1, hlog, mls), hb = hash_at(src + ip0 - 2, hlog, mls);
+            ht[ha] = cur0 + 2; wr[ha] = 0;
+            ht[hb] = (uint32_t)(ip0 - 2) + 1; wr[hb] = 0;
+            if (offset_2 > 0) {
+                while ((ip0 <= ilimit) && (rd32(src + ip0) == rd32(src + ip0 - offset_2))) {
+                    const size_t rLength = match_count(src, (size_t)ip0 + 4, (size_t)ip0 + 4 - offset_2, (size_t)iend) + 4;
+                    const uint32_t t = offset_2; offset_2 = offset_1; offset_1 = t;
+                    const uint32_t hr = hash_at(src + ip0, hlog, mls);
+                    ht[hr] = (uint32_t)ip0 + 1; wr[hr] = 0;
+                    row(ip0, 0, 3, 0, rLength, ip0 + (long)rLength == iend, 0, 0, 1);
+                    ip0 += (long)rLength;
+                    anchor = ip0;
+                }
+            }
+        }
+        ip1 = ip0 + 1;
+        segment++;
+        k = 0;
+    }
+    free(wr); free(ht);
+    return nbSeq;
+}
+
 // The encoder's no-match certificate (pgn_zenc.h no_match_certificate), serially: 1 when the
 // level-1 search of the single-block frame src[0, n) provably finds no match.
 static uint32_t cert_fmix32(uint32_t x)
