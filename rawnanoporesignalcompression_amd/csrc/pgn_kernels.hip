@@ -34,7 +34,6 @@ constexpr uint32_t kPassSamples = 262144;
 static_assert(PGN_MAX_CHUNK_SAMPLES >= kPassSamples, "chunk limits");
 // literals and sequences live per zstd block (<= 128 KiB); a frame's blocks reuse them
 constexpr uint32_t kMaxEncSeq = (uint32_t)z1::kMaxSrc / 4 + 2;  // every match covers >= 4 bytes
-constexpr uint32_t kMaxDecSeq = (uint32_t)z1::kMaxSrc / 3 + 2;  // any valid block: matches >= 3 bytes
 // every stream of the largest chunk fits one encoder frame (its svb16 buffer, ~2.13 n, the largest)
 static_assert((size_t)PGN_MAX_CHUNK_SAMPLES * 9 / 4 + 64 <= kMaxFrameBytes, "frame index field");
 constexpr int kStreams = 5;
@@ -101,7 +100,7 @@ __host__ __device__ inline EncLayout enc_layout()
 }
 
 struct DecLayout {
-    size_t lit, seqs, tables, htab, bytes;
+    size_t lit, tables, htab, bytes;
 };
 __host__ __device__ inline DecLayout dec_layout()
 {
@@ -109,7 +108,6 @@ __host__ __device__ inline DecLayout dec_layout()
     size_t o = 0;
     auto take = [&](size_t n) { size_t r = o; o = align_up(o + n + 64, 256); return r; };
     l.lit = take(z1::kMaxSrc);
-    l.seqs = take(12 * (size_t)kMaxDecSeq);
     l.tables = take(4 * ((size_t)kSeqTab + 4));
     l.htab = take(2u << z1::kHufTableLogMax);
     l.bytes = o;
@@ -675,8 +673,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void de
     uint8_t* sbase = a.slotScratch + (size_t)blockIdx.x * a.slotBytes;
     DecScratch S;
     S.lit = sbase + lay.lit;
-    S.seqs = (uint32_t*)(sbase + lay.seqs);
-    S.maxSeq = kMaxDecSeq;
     S.tables = (uint32_t*)(sbase + lay.tables);
     S.htab = (uint16_t*)(sbase + lay.htab);
     S.coopCmd = nullptr;
@@ -1178,8 +1174,6 @@ __global__ __launch_bounds__(64 * kCoopWaves) void dec_zstd_coop_kernel(DecArgs 
     uint8_t* sbase = a.slotScratch + (size_t)u * a.slotBytes;
     DecScratch S;
     S.lit = sbase + lay.lit;
-    S.seqs = (uint32_t*)(sbase + lay.seqs);
-    S.maxSeq = kMaxDecSeq;
     S.tables = (uint32_t*)(sbase + lay.tables);
     S.htab = (uint16_t*)(sbase + lay.htab);
     S.coopCmd = cmd;
@@ -1807,8 +1801,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void de
     uint8_t* sbase = a.slotScratch + (size_t)blockIdx.x * a.slotBytes;
     DecScratch S;
     S.lit = sbase + lay.lit;
-    S.seqs = (uint32_t*)(sbase + lay.seqs);
-    S.maxSeq = kMaxDecSeq;
     S.tables = (uint32_t*)(sbase + lay.tables);
     S.htab = (uint16_t*)(sbase + lay.htab);
     S.coopCmd = nullptr;

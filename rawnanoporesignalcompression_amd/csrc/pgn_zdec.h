@@ -75,8 +75,6 @@ static_assert(sizeof(DecLds) <= kCodecLdsBytes, "decoder LDS exceeds the codec L
 
 struct DecScratch {
     uint8_t* lit;           // literals of a block with sequences (<= 128 KiB)
-    uint32_t* seqs;         // decoded sequences: {litLength, matchLength, offset} triples
-    uint32_t maxSeq;
     uint32_t* tables;       // the three sequence FSE tables of a multi-block frame (kSeqTab + 4 words)
     uint16_t* htab;         // 4096 entries: a 12-bit Huffman table, or the parked LDS table
     uint8_t* job;           // this frame's HufJob record (pgn_hufjob.h): a literals-only last block's
@@ -479,15 +477,15 @@ __device__ __forceinline__ size_t huf_build_dtable_body(HufBuildLds& H, const ui
     }
     if (Pp) Pp->mark(15);
     lds_sync();
-    // HUF_readStats tail: implied last weight and table log (weights > 12 are corrupt)
+    // HUF_readStats tail: implied last weight and table log (weights >= 12 are corrupt)
     uint32_t w4[4];
     uint32_t wsum = 0, bad = 0, r1 = 0;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const uint32_t sym = 4u * (uint32_t)lane + (uint32_t)q;
         w4[q] = (sym < nbW) ? H.wts[sym] : 0u;
-        bad |= w4[q] > z1::kHufTableLogMax;
-        wsum += w4[q] > z1::kHufTableLogMax ? 0u : ((1u << w4[q]) >> 1);
+        bad |= w4[q] >= z1::kHufTableLogMax;
+        wsum += w4[q] >= z1::kHufTableLogMax ? 0u : ((1u << w4[q]) >> 1);
         r1 += w4[q] == 1;
     }
     if (ballot(bad != 0)) return 0;
@@ -906,8 +904,6 @@ __device__ __noinline__ long exec_sequences_wave(const uint8_t* seqSrc, size_t s
     op = uni((uint64_t)op);
     dstCap = uni((uint64_t)dstCap);
     frameStart = uni((uint64_t)frameStart);
-    S.seqs = uni(S.seqs);
-    S.maxSeq = uni(S.maxSeq);
     S.tables = uni(S.tables);
     // stage the section head (nbSeq, modes, table descriptions), zero padded
     const uint32_t nst = seqSize < (size_t)kSeqHdr - 16 ? (uint32_t)seqSize : (uint32_t)kSeqHdr - 16;
@@ -933,7 +929,8 @@ __device__ __noinline__ long exec_sequences_wave(const uint8_t* seqSrc, size_t s
     if (nbSeq == 0) {
         if (pos != srcSize) return z1::kDecErrCorrupt;
     } else {
-        if (nbSeq > S.maxSeq || pos >= srcSize) return z1::kDecErrCorrupt;
+        // any count the header can state (up to 0x7F00 + 0xFFFF): zero-bit sequences cost no input
+        if (pos >= srcSize) return z1::kDecErrCorrupt;
         const uint32_t modes = sDec.qhdr[pos++];
         uint32_t tlog[3];
 #pragma unroll 1
@@ -995,6 +992,14 @@ __device__ __noinline__ long exec_sequences_wave(const uint8_t* seqSrc, size_t s
         uint32_t sOF = seqbits_read(br, tlog[1]);
         uint32_t sML = seqbits_read(br, tlog[2]);
         size_t litPos = 0;
+        // Bits left over after the last sequence (zstd1_dec.h decode_sequences_exec): accepted up to what
+        // the state update after it would read.  The states are still the last sequence's, their
+        // entries still in sDec.qtab; read only when the stream does not end at its first bit.
+        auto endBad = [&]() -> bool {
+            if (br.pos == 0) return false;
+            const int32_t slack = (int32_t)((sDec.qtab[sLL] >> 24) + (sDec.qtab[512 + sOF] >> 24) + (sDec.qtab[768 + sML] >> 24));
+            return br.pos < 0 || br.pos > slack;
+        };
         P.mark(10);
         for (uint32_t b0 = 0; b0 < nbSeq; b0 += 64) {
             const uint32_t nb = (nbSeq - b0) < 64u ? nbSeq - b0 : 64u;
@@ -1043,7 +1048,7 @@ __device__ __noinline__ long exec_sequences_wave(const uint8_t* seqSrc, size_t s
                 fs.rep1 = rep1;
                 fs.rep2 = rep2;
                 fs.valid = valid;
-                const long r = exec_one_batch(lit, rs, dst, op, dstCap, nb, br.pos != 0);
+                const long r = exec_one_batch(lit, rs, dst, op, dstCap, nb, endBad());
                 P.mark(15);
                 return r;
             }
@@ -1074,7 +1079,7 @@ __device__ __noinline__ long exec_sequences_wave(const uint8_t* seqSrc, size_t s
             }
             P.mark(14);
         }
-        if (br.pos != 0) return z1::kDecErrCorrupt;
+        if (endBad()) return z1::kDecErrCorrupt;
         const size_t remLit = rs - litPos;
         if (op + remLit > dstCap) return z1::kDecErrDstSmall;
         wave_copy(dst + op, lit + litPos, remLit);
@@ -1159,8 +1164,6 @@ __device__ __noinline__ long zstd_decompress_wave(const uint8_t* __restrict__ sr
     dst = uni(dst);
     dstCap = uni((uint64_t)dstCap);
     S.lit = uni(S.lit);
-    S.seqs = uni(S.seqs);
-    S.maxSeq = uni(S.maxSeq);
     S.tables = uni(S.tables);
     S.htab = uni(S.htab);
     S.job = uni(S.job);
@@ -1232,10 +1235,9 @@ __device__ __noinline__ long zstd_decompress_wave(const uint8_t* __restrict__ sr
                 op += bsize;
             } else {
                 if (bsize > srcSize - ip) return z1::kDecErrSrcSmall;
-                if (bsize > z1::kMaxSrc) return z1::kDecErrCorrupt;
+                if (bsize >= z1::kMaxSrc || bsize < 3) return z1::kDecErrCorrupt;  // as zstd1_dec.h decompress_frames
                 const uint8_t* blk = src + ip;
                 // ---- literals section header
-                if (bsize < 1) return z1::kDecErrCorrupt;
                 const uint32_t b0 = hw_byte(hw, src, ip);
                 const unsigned ltype = b0 & 3, sf = (b0 >> 2) & 3;
                 size_t lh, rs, cs = 0;
@@ -1393,7 +1395,7 @@ __device__ __forceinline__ long dec_frame_fast(const uint8_t* __restrict__ src, 
         P.mark(5);
         return (long)bsize;
     }
-    if (btype != z1::kBtCompressed || job == nullptr || bsize > z1::kMaxSrc || bsize < 5) return -1;
+    if (btype != z1::kBtCompressed || job == nullptr || bsize >= z1::kMaxSrc || bsize < 5) return -1;
     const uint32_t lhc = hw_u32(hw, src, ip);
     const unsigned ltype = lhc & 3, sf = (lhc >> 2) & 3;
     if (ltype != z1::kSetCompressed || sf == 0) return -1;

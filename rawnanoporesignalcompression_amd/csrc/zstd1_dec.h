@@ -391,7 +391,7 @@ PGN_HD unsigned huf_complete_weights(uint8_t* weights, unsigned nbW)
     for (unsigned i = 0; i < kHufTableLogMax + 2; i++) rankStats[i] = 0;
     uint32_t weightTotal = 0;
     for (unsigned n = 0; n < nbW; n++) {
-        if (weights[n] > kHufTableLogMax) return 0;
+        if (weights[n] >= kHufTableLogMax) return 0;  // HUF_readStats: a weight is below HUF_TABLELOG_MAX
         rankStats[weights[n]]++;
         weightTotal += (1u << weights[n]) >> 1;
     }
@@ -616,6 +616,7 @@ PGN_HD long decode_sequences_exec(const uint8_t* src, size_t srcSize, const uint
     uint32_t sOF = br_read(br, w.of.tableLog);
     uint32_t sML = br_read(br, w.ml.tableLog);
     size_t litPos = 0;
+    int64_t endSlack = 0;  // bits the state update after the last sequence would read
     for (size_t i = 0; i < nbSeq; i++) {
         const FseDEntry eLL = w.ll.e[sLL], eOF = w.of.e[sOF], eML = w.ml.e[sML];
         unsigned ofCode = eOF.symbol, mlCode = eML.symbol, llCode = eLL.symbol;
@@ -645,6 +646,8 @@ PGN_HD long decode_sequences_exec(const uint8_t* src, size_t srcSize, const uint
             sLL = eLL.newState + br_read(br, eLL.nbBits);
             sML = eML.newState + br_read(br, eML.nbBits);
             sOF = eOF.newState + br_read(br, eOF.nbBits);
+        } else {
+            endSlack = (int64_t)eLL.nbBits + eML.nbBits + eOF.nbBits;
         }
         // execute
         if (litPos + ll > litSize) return kDecErrCorrupt;
@@ -656,7 +659,9 @@ PGN_HD long decode_sequences_exec(const uint8_t* src, size_t srcSize, const uint
         for (uint32_t k = 0; k < ml; k++) out[op + k] = out[(long)op + (long)k - (long)offset];
         op += ml;
     }
-    if (br.pos != 0) return kDecErrCorrupt;
+    // libzstd 1.4.x updates the states after the last sequence too and then asks only that the stream
+    // is used up: bits left over are accepted as long as that update would have read them all
+    if (br.pos < 0 || br.pos > endSlack) return kDecErrCorrupt;
     size_t rem = litSize - litPos;
     if (op + rem > outCap) return kDecErrDstSmall;
     for (size_t k = 0; k < rem; k++) out[op + k] = lit[litPos + k];
@@ -736,7 +741,9 @@ PGN_HD long decompress_frames(const uint8_t* src, size_t srcSize, uint8_t* dst, 
                 op += bsize;
             } else {
                 if (bsize > srcSize - ip) return kDecErrSrcSmall;
-                if (bsize > kMaxSrc) return kDecErrCorrupt;
+                // ZSTD_decompressBlock_internal: srcSize < ZSTD_BLOCKSIZE_MAX; ZSTD_decodeLiteralsBlock:
+                // srcSize >= MIN_CBLOCK_SIZE (3)
+                if (bsize >= kMaxSrc || bsize < 3) return kDecErrCorrupt;
                 const uint8_t* lit;
                 size_t litSize;
                 size_t lc = decode_literals(src + ip, bsize, w, &lit, &litSize);
