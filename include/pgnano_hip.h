@@ -464,6 +464,83 @@ int pgn_segment_reads_device(pgn_ctx *ctx, size_t nreads, const int16_t *d_sampl
                              pgn_segment *d_segments, pgn_read_segments *d_reads, pgn_read_stats *d_stats,
                              uint64_t *d_total, void *stream);
 
+/* ---- Model output back to reads -----------------------------------------------------------------------
+ * The inverse of the cut above, for what a model makes of the rows: a model of stride s turns a row of L
+ * samples into T = L / s frames of some fixed number of bytes; neighbouring rows of a read overlap, so their
+ * frames are doubled there.  The plan call decides, from the index the segment call left, which frames of
+ * every row are kept and where they go; the rows call copies the kept frames of one model batch into a dense
+ * per-read layout.  Every output is exact: an index computation and a byte copy.  No outside source defines
+ * the rule, so this text does.
+ *
+ * Parameters (pgn_stitch_params: length L, overlap V, frame_samples s): 1 <= s, L % s == 0, s <= L - V,
+ * L <= 2^24; T = L / s.  L and V must be the ones the segments were cut with; nothing can check that.
+ *
+ * A read is taken when its pgn_read_segments.status is PGN_OK, it has k = nsegments >= 1 segments and all of
+ * them lie below segment_capacity.  For its segments j = 0..k-1 let a_j = start_j - start_0 and valid_j be
+ * those of the segment table.  Cut points, in samples of the trimmed read:
+ *   c_j     = a_{j+1} + floor((a_j + L - a_{j+1}) / 2)   for j < k-1  (the middle of the overlap)
+ *   c_{k-1} = a_{k-1} + valid_{k-1}                       (the read's end)
+ *   c_{-1}  = 0
+ * Segment j owns the samples [c_{j-1}, c_j).  Frame f of segment j is kept iff its first sample a_j + f * s
+ * lies in what its segment owns:
+ *   first_j = ceil((c_{j-1} - a_j) / s)
+ *   end_j   = min(T, ceil((c_j - a_j) / s))
+ *   count_j = max(0, end_j - first_j)
+ * The read's frames are the kept frames of its segments in segment order, frames_r = sum count_j; reads
+ * follow each other in read order, and d_read_frames (nreads + 1 entries) is the exclusive scan of frames_r.
+ * pgn_stitch_segment (one per table row): frames [first, first + count) of the row are kept, and `dst_frame`
+ * is the index of the first of them in that layout, d_read_frames[read] + sum of count_i over i < j.
+ * A read that is not taken (another status, PGN_ERR_DST_TOO_SMALL included, whose later segments were never
+ * written; no segments; or a segment at or above segment_capacity) yields no frames: its plan entries below
+ * the capacity have first = 0, count = 0 and dst_frame = d_read_frames[read].  Table entries at or above
+ * segment_capacity are never read; plan entries [0, min(total, segment_capacity)) are written, total being
+ * the segment count of the pgn_read_segments array.
+ * What follows from the rule: the kept frames' first samples rise strictly and lie in [0, m) for a trimmed
+ * read of m samples; |frames_r - ceil(m / s)| <= k - 1; frames_r <= ceil(n / s) + segments(n) for every
+ * untrimmed length n >= m, which is the bound a host can take without a wait.  Where 2s divides V, s divides
+ * L - V and the read ends on the segment grid, h = V / (2s) frames are dropped on each side of every joint
+ * (segment 0 keeps [0, T - h), the last [h, T), the inner ones [h, T - h)) and frames_r = ceil(m / s).
+ *
+ * pgn_stitch_plan_device: asynchronous on `stream`, no host wait; its scratch lives on the context and grows
+ * with segment_capacity.  With segment_capacity == 0, d_segments and d_plan may be NULL.
+ *
+ * pgn_stitch_rows_device copies the kept frames of table rows [first_segment, + nsegments), one model batch
+ * whose output lies at d_rows: frame f of table row g is the frame_bytes contiguous bytes at
+ *   d_rows + (g - first_segment) * row_stride_bytes + f * frame_stride_bytes
+ * (an [N, T, C] output has row stride T * C and frame stride C elements, a [T, N, C] output C and N * C), and
+ * goes to
+ *   d_out + (dst_frame + (f - first) - out_frame_base) * frame_bytes.
+ * A frame whose destination index dst_frame + (f - first) - out_frame_base lies outside
+ * [0, out_capacity_frames) is not written, and nothing but the kept frames' bytes is written.  d_plan is the
+ * whole plan (it is indexed by g).  A frame at or above T is never read, whatever the plan says.  Any
+ * alignment of d_rows, d_out and the strides is allowed; 16-byte moves are used where the destination
+ * allows.  d_rows and d_out must not overlap.  Asynchronous on `stream`, no host wait, no scratch.
+ *
+ * PGN_ERR_INVALID_ARG before any GPU call, checking in this order: a NULL ctx or params; the parameter
+ * constraints above; then for the plan call a NULL d_read_frames and, with nreads > 0, a NULL d_reads, a NULL
+ * d_segments or d_plan with segment_capacity > 0, nreads >= 2^32, or segment_capacity >= 2^40 (with
+ * nreads == 0 only d_read_frames[0] = 0 is written); for the rows call frame_bytes == 0, frame_stride_bytes < frame_bytes unless T == 1, then, with
+ * nsegments > 0, a NULL d_plan, d_rows or d_out.
+ * Not covered: decoding itself; stitching of decoded sequences or move tables; models whose T != L / s
+ * (padding or valid convolutions); stitching in place. */
+typedef struct pgn_stitch_params {
+    uint32_t length, overlap, frame_samples;
+    uint32_t pad;
+} pgn_stitch_params;
+typedef struct pgn_stitch_segment {
+    uint64_t dst_frame;
+    uint32_t first, count;
+} pgn_stitch_segment;
+
+int pgn_stitch_plan_device(pgn_ctx *ctx, size_t nreads, const pgn_read_segments *d_reads,
+                           const pgn_segment *d_segments, uint64_t segment_capacity,
+                           const pgn_stitch_params *params, pgn_stitch_segment *d_plan, uint64_t *d_read_frames,
+                           void *stream);
+int pgn_stitch_rows_device(pgn_ctx *ctx, const pgn_stitch_params *params, const pgn_stitch_segment *d_plan,
+                           uint64_t first_segment, uint64_t nsegments, const void *d_rows,
+                           uint64_t row_stride_bytes, uint64_t frame_stride_bytes, uint32_t frame_bytes,
+                           void *d_out, uint64_t out_frame_base, uint64_t out_capacity_frames, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

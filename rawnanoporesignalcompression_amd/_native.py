@@ -83,6 +83,16 @@ class Segment(C.Structure):
     _fields_ = [("read", C.c_uint32), ("start", C.c_uint32), ("valid", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class StitchParams(C.Structure):
+    """pgn_stitch_params"""
+    _fields_ = [("length", C.c_uint32), ("overlap", C.c_uint32), ("frame_samples", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class StitchSegment(C.Structure):
+    """pgn_stitch_segment"""
+    _fields_ = [("dst_frame", C.c_uint64), ("first", C.c_uint32), ("count", C.c_uint32)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -145,6 +155,10 @@ SIGNATURES = [
     ("pgn_segment_reads_device", C.c_int,
      [_VP, _SZ, _VP, _U64P, _U64P, _I32P, C.POINTER(TrimParams), C.POINTER(NormParams), C.POINTER(SegmentParams), _VP,
       C.c_int, C.c_uint64, _VP, _VP, _VP, _U64P, _VP]),
+    ("pgn_stitch_plan_device", C.c_int, [_VP, _SZ, _VP, _VP, C.c_uint64, C.POINTER(StitchParams), _VP, _U64P, _VP]),
+    ("pgn_stitch_rows_device", C.c_int,
+     [_VP, C.POINTER(StitchParams), _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, C.c_uint64, C.c_uint32, _VP,
+      C.c_uint64, C.c_uint64, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

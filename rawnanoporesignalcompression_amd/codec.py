@@ -24,6 +24,9 @@ device-resident torch tensors: one launch encodes or decodes every chunk of a ba
 quantiles or median / MAD; :meth:`PGNanoCodec.read_stats` gives those statistics for decoded reads.
 :meth:`PGNanoCodec.segment_reads` trims the head of decoded reads, normalises them and cuts them into the
 ``[segments, length]`` tensor a model reads (:func:`trim_signal` and :func:`segment_signal` on the host).
+:meth:`PGNanoCodec.stitch_plan` and :meth:`PGNanoCodec.stitch` undo that cut for the model's output: they drop
+the frames doubled where rows overlap and lay each read's frames end to end (:func:`stitch_plan_signal` on the
+host).
 """
 from __future__ import annotations
 
@@ -304,6 +307,61 @@ def segment_signal(adc, length, overlap, trim=None, dtype=np.float16, **norm):
         for j, (start, valid) in enumerate(plan):
             rows[j, :valid] = z[start:start + valid]
     return rows
+
+
+class StitchTable(_Columns):
+    """``pgn_stitch_segment`` of every segment: frames ``[first, first + count)`` of the row are kept and go to
+    frame ``dst_frame`` (int64) on; ``first`` and ``count`` int32."""
+
+    DTYPE = np.dtype([("dst_frame", "<u8"), ("first", "<u4"), ("count", "<u4")])
+    _COLS = {"dst_frame": ("int64", 0), "first": ("int32", 2), "count": ("int32", 3)}
+
+
+@dataclass
+class StitchPlan:
+    """What :meth:`PGNanoCodec.stitch_plan` leaves on the device."""
+    segments: StitchTable   # one entry per row of the segment table it was made from
+    read_frames: "object"   # int64, reads + 1: read r's frames are [read_frames[r], read_frames[r + 1])
+    params: "object"        # the pgn_stitch_params it was made with
+
+
+def stitch_params(length, overlap, frame_samples):
+    """``pgn_stitch_params``: the ``length`` and ``overlap`` the segments were cut with and the model's stride
+    ``frame_samples``, which divides ``length`` and does not exceed ``length - overlap``."""
+    L, V, s = int(length), int(overlap), int(frame_samples)
+    if not (1 <= s and 1 <= L <= 1 << 24 and L % s == 0 and 0 <= V and s <= L - V):
+        raise ValueError("need 1 <= frame_samples, length % frame_samples == 0, 0 <= overlap, frame_samples <= "
+                         f"length - overlap and length <= 2^24 (got {L}, {V}, {s})")
+    return _native.StitchParams(L, V, s, 0)
+
+
+def stitch_plan_signal(m_or_segments, length, overlap, frame_samples):
+    """The kept frames of one read's segments on the host (include/pgnano_hip.h, "Model output back to
+    reads"): ``[segments, 2]`` int64, ``first`` and ``count`` per segment.  ``m_or_segments`` is the trimmed
+    read's length, or its segments as ``(start, valid)`` rows of the segment table (any common origin of the
+    starts).  :meth:`PGNanoCodec.stitch_plan` writes these values for a read that is taken."""
+    p = stitch_params(length, overlap, frame_samples)
+    L, s, T = p.length, p.frame_samples, p.length // p.frame_samples
+    segs = _segment_starts(int(m_or_segments), L, p.overlap) if np.isscalar(m_or_segments) else m_or_segments
+    segs = np.asarray(segs, dtype=np.int64).reshape(-1, 2)
+    k = segs.shape[0]
+    if k == 0:
+        return np.zeros((0, 2), np.int64)
+    a, valid = segs[:, 0] - segs[0, 0], segs[:, 1]
+    half = (a[:-1] + L - a[1:]) // 2           # half the overlap of segments j and j + 1, rounded down
+    lo = np.concatenate([[0], half])           # c_{j-1} - a_j
+    hi = np.concatenate([a[1:] - a[:-1] + half, valid[-1:]])  # c_j - a_j
+    first = np.minimum(-(-lo // s), T)
+    end = np.minimum(-(-hi // s), T)
+    return np.stack([first, np.maximum(end - first, 0)], 1)
+
+
+def stitch_bound(counts, length, overlap, frame_samples) -> int:
+    """The frames a batch of reads of these (untrimmed) lengths can give: ``ceil(n / s) + segments(n)`` per
+    read bounds the frames of every trimmed length, so this is an upper bound computed on the host."""
+    p = stitch_params(length, overlap, frame_samples)
+    n = np.asarray(counts).astype(np.int64).reshape(-1)
+    return int((-(-n // p.frame_samples)).sum()) + segment_bound(n, p.length, p.overlap)
 
 
 @dataclass
@@ -687,6 +745,89 @@ class PGNanoCodec:
                 _ptr(out), types[dtype], capacity, _ptr(segs), _ptr(reads), _ptr(raw), _ptr(total), ls.cuda_stream))
         caller.wait_stream(ls)
         return SegmentedReads(out, SegmentTable(segs), ReadSegments(reads), ReadStats(raw), total)
+
+    def stitch_plan(self, segmented: SegmentedReads, length, overlap, frame_samples, capacity=None,
+                    stream: int | None = None) -> StitchPlan:
+        """Which frames of a model's output for every row of ``segmented`` are kept, and where they go when the
+        reads are laid end to end (pgn_stitch_plan_device): a model of stride ``frame_samples`` gives
+        ``length // frame_samples`` frames per row, and rows of one read overlap.  ``length`` and ``overlap`` are
+        the ones ``segmented`` was cut with.  Per read :func:`stitch_plan_signal` of its table rows; a read whose
+        status is not 0 (or that the capacity cuts) gives no frames.  capacity: the rows of the segment table
+        that may be read (default: all it has).  No host wait."""
+        import torch
+
+        prm = stitch_params(length, overlap, frame_samples)
+        segs, reads = segmented.segments.raw, segmented.reads.raw
+        _require_device(reads, "segmented.reads", self.device)
+        _require_device(segs, "segmented.segments", self.device)
+        if not (segs.is_contiguous() and reads.is_contiguous()):
+            raise ValueError("the tables of segmented must be contiguous")
+        capacity = int(segs.shape[0]) if capacity is None else int(capacity)
+        if not 0 <= capacity <= int(segs.shape[0]):
+            raise ValueError(f"capacity must lie in [0, {int(segs.shape[0])}], the rows of the segment table")
+        n = int(reads.shape[0])
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = reads.device
+            plan = torch.zeros((capacity, C.sizeof(_native.StitchSegment)), dtype=torch.uint8, device=dev)
+            frames = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            _check(self._lib.pgn_stitch_plan_device(self._h, n, _ptr(reads), _ptr(segs), capacity, C.byref(prm),
+                                                    _ptr(plan), _ptr(frames), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return StitchPlan(StitchTable(plan), frames, prm)
+
+    def stitch(self, plan: StitchPlan, rows, first_segment: int = 0, out=None, frame_base: int = 0,
+               time_major: bool = False, stream: int | None = None):
+        """The kept frames of one model batch, copied to where ``plan`` puts them (pgn_stitch_rows_device).
+
+        rows: the model's output for table rows ``[first_segment, first_segment + N)``, a tensor of any dtype,
+        ``[N, T, ...]`` or with ``time_major`` ``[T, N, ...]``; the trailing dimensions form the frame and must
+        be contiguous, the first two may have any strides.  out: ``[frames, ...]`` contiguous, of rows' dtype
+        and frame shape; frame ``i`` of the stitched reads goes to ``out[i - frame_base]`` and a frame outside
+        ``out`` is not written, so a batch may be stitched into a buffer of its own (``frame_base`` = its first
+        ``dst_frame``) or all batches into one.  Without ``out`` one is allocated for every frame from
+        ``frame_base`` on, which waits for ``plan.read_frames[-1]``.  Returns ``out``; nothing but kept
+        frames is written to it."""
+        import torch
+
+        prm = plan.params
+        T = prm.length // prm.frame_samples
+        _require_device(rows, "rows", self.device)
+        if rows.dim() < 2:
+            raise ValueError("rows must have at least the two dimensions [N, T] (or [T, N])")
+        nd, td = (1, 0) if time_major else (0, 1)
+        N = int(rows.shape[nd])
+        if int(rows.shape[td]) != T:
+            raise ValueError(f"rows must have {T} frames per row (got {int(rows.shape[td])})")
+        frame_shape = tuple(rows.shape[2:])
+        item = rows.element_size()
+        frame_bytes = item * int(np.prod(frame_shape, dtype=np.int64))
+        if frame_bytes == 0:
+            raise ValueError("a frame must have at least one element")
+        expect = 1
+        for size, stride in zip(reversed(frame_shape), reversed(rows.stride()[2:])):
+            if size != 1 and stride != expect:
+                raise ValueError("the trailing dimensions of rows (the frame) must be contiguous")
+            expect *= size
+        first_segment, frame_base = int(first_segment), int(frame_base)
+        if first_segment < 0 or frame_base < 0 or first_segment + N > len(plan.segments):
+            raise ValueError(f"rows [{first_segment}, {first_segment + N}) are not all in the plan's {len(plan.segments)}")
+        if out is None:
+            total = int(plan.read_frames[-1].item())
+            out = torch.empty((max(total - frame_base, 0),) + frame_shape, dtype=rows.dtype, device=rows.device)
+        else:
+            _require_device(out, "out", self.device)
+            if out.dtype != rows.dtype or tuple(out.shape[1:]) != frame_shape or out.dim() < 1 or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous [frames{''.join(', %d' % d for d in frame_shape)}] tensor of {rows.dtype}")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            _check(self._lib.pgn_stitch_rows_device(
+                self._h, C.byref(prm), _ptr(plan.segments.raw), first_segment, N, _ptr(rows), int(rows.stride(nd)) * item,
+                int(rows.stride(td)) * item, frame_bytes, _ptr(out), frame_base, int(out.shape[0]), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return out
 
     def decompress_reads_norm(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, *,
                               mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0,

@@ -7,6 +7,7 @@
 #define PGN_SELECT_HOST_ONLY
 #include "pgn_segment.h"
 #include "pgn_select.h"
+#include "pgn_stitch.h"
 #include "zstd1_dec.h"
 #include "zstd1_model.h"
 
@@ -301,6 +302,20 @@ int pgnm_segment_plan(uint64_t m, const pgn_segment_params* prm, uint64_t* nseg,
         start[j] = segment_start(m, L, S, j);
         valid[j] = segment_valid(m, L);
     }
+    return 0;
+}
+
+// The kept frames (pgn_stitch.h) of a taken read's k segments, given their table starts and valid counts:
+// the function the plan kernel runs per row.  Returns 0, or -1 for parameters the C ABI rejects.
+int pgnm_stitch_frames(const pgn_stitch_params* prm, uint64_t k, const uint32_t* start, const uint32_t* valid,
+                       uint32_t* first, uint32_t* count)
+{
+    using namespace pgn::stitch;
+    if (!params_valid(prm)) return -1;
+    const uint32_t L = prm->length, s = prm->frame_samples, T = L / s;
+    for (uint64_t j = 0; j < k; j++)
+        kept_frames(j ? start[j - 1] : 0, start[j], j + 1 < k ? start[j + 1] : 0, valid[j], j == 0, j + 1 == k, L, s, T,
+                    first[j], count[j]);
     return 0;
 }
 

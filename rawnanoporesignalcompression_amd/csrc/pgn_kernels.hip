@@ -19,6 +19,7 @@
 #include "pgn_c5.h"
 #include "pgn_internal.h"
 #include "pgn_segment.h"
+#include "pgn_stitch.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2122,6 +2123,9 @@ struct pgn_ctx {
     // trimmed read's statistics; then the segment total (one block, carved up by ensure_segment)
     uint8_t* segWork = nullptr;
     size_t segReads = 0;
+    // pgn_stitch_plan_device: the frame totals of the count kernel's workgroups, then their sum
+    uint64_t* stitchSums = nullptr;
+    size_t stitchBlocks = 0;
     // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
     // first work items and the slots in one block sized by max_split_reads; the per-read counts the one-workgroup kernel reads.
     // Defaults measured by tools/select_split_timing.py (profiles/select_split_timing.log)
@@ -2321,6 +2325,7 @@ int pgn_ctx_destroy(pgn_ctx* c)
     (void)hipFree(c->normReadN);
     (void)hipFree(c->normStats);
     (void)hipFree(c->segWork);
+    (void)hipFree(c->stitchSums);
     (void)hipFree(c->splitWork);
     (void)hipFree(c->splitWholeCounts);
     if (c->largeHdrHost) (void)hipHostFree(c->largeHdrHost);
@@ -3701,6 +3706,102 @@ extern "C" int pgn_segment_reads_device(pgn_ctx* c, size_t nreads, const int16_t
             hipLaunchKernelGGL(seg::segment_write_kernel<_Float16>, grid, dim3(seg::kWriteThreads), 0, s, wa);
         HIPCHK(hipGetLastError());
     }
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return PGN_OK;
+}
+
+// ---- model output back to reads (pgn_stitch.h) ----------------------------------------------------
+static int ensure_stitch(pgn_ctx* c, size_t nblocks)
+{
+    if (nblocks > c->stitchBlocks) {
+        wait_last_host(c);
+        (void)hipFree(c->stitchSums);
+        c->stitchSums = nullptr;
+        c->stitchBlocks = 0;
+        HIPCHK(hipMalloc(&c->stitchSums, (nblocks + 1) * sizeof(uint64_t)));
+        c->stitchBlocks = nblocks;
+    }
+    return PGN_OK;
+}
+
+extern "C" int pgn_stitch_plan_device(pgn_ctx* c, size_t nreads, const pgn_read_segments* d_reads,
+                                      const pgn_segment* d_segments, uint64_t segment_capacity,
+                                      const pgn_stitch_params* params, pgn_stitch_segment* d_plan,
+                                      uint64_t* d_read_frames, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!stitch::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if (!d_read_frames) return PGN_ERR_INVALID_ARG;
+    if (nreads) {
+        if (!d_reads) return PGN_ERR_INVALID_ARG;
+        if (segment_capacity && (!d_segments || !d_plan)) return PGN_ERR_INVALID_ARG;
+        if (nreads > 0xFFFFFFFFull) return PGN_ERR_INVALID_ARG;  // a segment's read index is 32-bit
+        if (segment_capacity >> 40) return PGN_ERR_INVALID_ARG;  // the count kernel's grid
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    if (nreads == 0) {
+        HIPCHK(hipMemsetAsync(d_read_frames, 0, sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    const uint64_t nblocks = std::max<uint64_t>(1, (segment_capacity + stitch::kPlanThreads - 1) / stitch::kPlanThreads);
+    const int rc = ensure_stitch(c, (size_t)nblocks);
+    if (rc != PGN_OK) return rc;
+    const stitch::PlanArgs pa{nreads, d_reads, d_segments, segment_capacity, params->length, params->frame_samples,
+                              params->length / params->frame_samples, d_plan, c->stitchSums, nblocks, d_read_frames};
+    hipLaunchKernelGGL(stitch::stitch_count_kernel, dim3((unsigned)nblocks), dim3(stitch::kPlanThreads), 0, s, pa);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, pa);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(stitch::stitch_offset_kernel, dim3((unsigned)nblocks), dim3(stitch::kPlanThreads), 0, s, pa);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(stitch::stitch_read_frames_kernel, dim3((unsigned)(nreads / 256 + 1)), dim3(256), 0, s, pa);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return PGN_OK;
+}
+
+extern "C" int pgn_stitch_rows_device(pgn_ctx* c, const pgn_stitch_params* params, const pgn_stitch_segment* d_plan,
+                                      uint64_t first_segment, uint64_t nsegments, const void* d_rows,
+                                      uint64_t row_stride_bytes, uint64_t frame_stride_bytes, uint32_t frame_bytes,
+                                      void* d_out, uint64_t out_frame_base, uint64_t out_capacity_frames, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!stitch::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    const uint32_t T = params->length / params->frame_samples;
+    if (frame_bytes == 0) return PGN_ERR_INVALID_ARG;
+    if (frame_stride_bytes < frame_bytes && T != 1) return PGN_ERR_INVALID_ARG;
+    if (nsegments == 0) return PGN_OK;
+    if (!d_plan || !d_rows || !d_out) return PGN_ERR_INVALID_ARG;
+    if (out_capacity_frames == 0) return PGN_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    // a piece (a dense row's kept frames, or one frame of a strided row) is shared by the smallest power of
+    // two of threads that covers its 16-byte units -- its bytes, up to 32, where the destination is not known
+    // to fall on 16-byte boundaries -- up to the workgroup
+    const bool dense = frame_stride_bytes == frame_bytes || T == 1;
+    const bool alignedDst = ((uintptr_t)d_out & 15u) == 0 && frame_bytes % 16 == 0;
+    const uint64_t pieceBytes = dense ? (uint64_t)T * frame_bytes : frame_bytes;
+    uint64_t units = (pieceBytes + 15) / 16;
+    if (!alignedDst) units = std::max<uint64_t>(units, std::min<uint64_t>(pieceBytes, 32));
+    uint32_t log2Tpr = 0;
+    while (log2Tpr < 8 && (1ull << log2Tpr) < units) log2Tpr++;
+    const uint32_t slots = stitch::kRowsThreads >> log2Tpr;
+    const uint64_t blocks = dense ? (nsegments + slots - 1) / slots : nsegments;
+    const uint64_t perPart = 4ull * (dense ? stitch::kRowsThreads : slots);
+    const uint32_t split = (uint32_t)std::min<uint64_t>(stitch::kRowsSplit, std::max<uint64_t>(1, (dense ? units : T) / perPart));
+    const dim3 grid((unsigned)std::min<uint64_t>(blocks, 1u << 20), split);
+    const stitch::RowsArgs ra{d_plan + first_segment, nsegments, static_cast<const uint8_t*>(d_rows), row_stride_bytes,
+                              frame_stride_bytes, frame_bytes, T, static_cast<uint8_t*>(d_out), out_frame_base,
+                              out_capacity_frames, log2Tpr, dense ? 1u : 0u};
+    hipLaunchKernelGGL(stitch::stitch_rows_kernel, grid, dim3(stitch::kRowsThreads), 0, s, ra);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->evLast, s));
     c->haveLast = true;
     return PGN_OK;
