@@ -541,6 +541,80 @@ int pgn_stitch_rows_device(pgn_ctx *ctx, const pgn_stitch_params *params, const 
                            uint64_t row_stride_bytes, uint64_t frame_stride_bytes, uint32_t frame_bytes,
                            void *d_out, uint64_t out_frame_base, uint64_t out_capacity_frames, void *stream);
 
+/* ---- Stitched frames to bases -------------------------------------------------------------------------
+ * The best-path (greedy) CTC decode of the frames the rows call laid end to end: per read its base sequence
+ * and per base its frame and score; and, as a call of its own, the second half of it, which turns one code
+ * byte per frame into bases.  Every output is a selection, so the tolerance is zero.  No outside source defines
+ * the rule, so this text does.
+ *
+ * Frames are those of the dense per-read layout: frame i has C = classes scores of one type (PGN_OUT_F32 or
+ * PGN_OUT_F16), d_read_frames (nreads + 1 entries) is the plan's exclusive scan, read r has the frames i in
+ * [read_frames[r], read_frames[r+1]), and t = i - read_frames[r].
+ *   Label     l_i = argmax_c scores_i[c] as numpy.argmax computes it: IEEE comparison (-0 == +0), the lowest
+ *             index wins a tie, a NaN beats every number and the first NaN wins.  float16 scores are compared
+ *             as their exact float32 values.
+ *   Emission  frame i emits a base iff l_i != blank and (t == 0 or l_i != l_{i-1}).  The first frame of a read
+ *             looks at no predecessor, even if the previous read ended on the same label.
+ *   Code      code_i = l_i | 0x80 if the frame emits, else l_i: one byte per frame, which is why C <= 64.
+ *   Bases     read r's bases are alphabet[l_i] of its emitting frames in frame order, bases_r of them.
+ *             d_read_bases (nreads + 1) is the exclusive scan of bases_r over the reads in read order.  Base j
+ *             of read r has the global index g = read_bases[r] + j; with i its emitting frame
+ *               seq[g] = alphabet[l_i], base_frame[g] = t, base_score[g] = (float)scores_i[l_i]
+ *             (the float16-to-float32 widening is exact).
+ * Taken reads and the window.  The call sees frames [frame_base, frame_base + frame_capacity); frame i lies at
+ * d_frames + (i - frame_base) * frame_stride_bytes.  A read is taken iff
+ *   frame_base <= read_frames[r] <= read_frames[r+1] <= frame_base + frame_capacity.
+ * A read that is not taken gives bases_r = 0 and status PGN_ERR_INVALID_ARG, and none of its frames is read;
+ * read_frames is device data, so this per-read check is also what keeps every access inside the buffers.  A
+ * caller may therefore decode the reads that are complete inside one stitched batch buffer.
+ * Capacity.  A base with g >= base_capacity is not written to seq, base_frame or base_score.  A taken read with
+ * bases_r > 0 and read_bases[r+1] > base_capacity gets PGN_ERR_DST_TOO_SMALL, every other taken read PGN_OK.
+ * read_bases always holds the full counts, so read_bases[nreads] is the capacity that would have sufficed;
+ * bases_r <= frames_r, so the frame count is the bound a host can take without a wait.
+ * Codes.  d_codes[i - frame_base] is written for every frame of a taken read when the caller passes the
+ * array (without it the codes live in context scratch).  Nothing else in any output is written.  If read_frames
+ * does not ascend, the reads with read_frames[r] > read_frames[r+1] are not taken; the rest is unspecified,
+ * except that no access leaves the window or the buffers.
+ *
+ * pgn_collapse_codes_device is the second half applied to the caller's codes, whatever made them: a frame
+ * emits iff bit 7 of its code is set, and its base is alphabet[code & 0x7f] (128 entries).  Two emitting frames
+ * in a row with the same class give two bases.  Taken reads, capacity, statuses and read_bases follow the rule
+ * above; base_frame[g] = t.
+ *
+ * Both calls are asynchronous on `stream` with no host wait; their scratch lives on the context (16 bytes per
+ * PGN_CTC_TILE_FRAMES frames of frame_capacity, and frame_capacity bytes for a decode without d_codes).
+ * PGN_CTC_TILE_FRAMES is the number of frames one workgroup handles.
+ *
+ * PGN_ERR_INVALID_ARG before any GPU call, checking in this order: a NULL ctx, or NULL params (decode) or
+ * alphabet (collapse); classes outside 2..64, blank >= classes, score_type not PGN_OUT_F32 or PGN_OUT_F16, or
+ * pad != 0; frame_stride_bytes < C * the element size, or d_frames or frame_stride_bytes not a multiple of the
+ * element size; nreads >= 2^32 or frame_capacity >= 2^40; a NULL d_read_bases; with nreads > 0 a NULL
+ * d_read_frames or d_read_status; with frame_capacity > 0 a NULL d_frames (d_codes in the collapse call); with
+ * base_capacity > 0 a NULL d_seq.  With nreads == 0 only d_read_bases[0] = 0 is written.
+ * Not covered: CRF or transducer decoding and beam search; quality strings (phred calibration); decoding the
+ * rows before stitching; bfloat16 scores. */
+#define PGN_CTC_TILE_FRAMES 1024
+typedef struct pgn_ctc_params {
+    uint32_t classes;       /* C, 2..64 */
+    uint32_t blank;         /* < C */
+    uint32_t score_type;    /* PGN_OUT_F32 or PGN_OUT_F16 */
+    uint32_t pad;
+    uint8_t  alphabet[64];  /* byte written for class c; the blank's entry is not used */
+} pgn_ctc_params;
+
+int pgn_ctc_decode_device(pgn_ctx *ctx, const pgn_ctc_params *params, size_t nreads,
+                          const uint64_t *d_read_frames, const void *d_frames, uint64_t frame_stride_bytes,
+                          uint64_t frame_base, uint64_t frame_capacity,
+                          uint8_t *d_seq, uint64_t base_capacity, uint64_t *d_read_bases, int32_t *d_read_status,
+                          uint32_t *d_base_frame /* may be NULL */, float *d_base_score /* may be NULL */,
+                          uint8_t *d_codes /* may be NULL: context scratch is used */, void *stream);
+
+int pgn_collapse_codes_device(pgn_ctx *ctx, const uint8_t alphabet[128], size_t nreads,
+                              const uint64_t *d_read_frames, const uint8_t *d_codes, uint64_t frame_base,
+                              uint64_t frame_capacity,
+                              uint8_t *d_seq, uint64_t base_capacity, uint64_t *d_read_bases, int32_t *d_read_status,
+                              uint32_t *d_base_frame /* may be NULL */, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

@@ -93,6 +93,15 @@ class StitchSegment(C.Structure):
     _fields_ = [("dst_frame", C.c_uint64), ("first", C.c_uint32), ("count", C.c_uint32)]
 
 
+PGN_CTC_TILE_FRAMES = 1024
+
+
+class CtcParams(C.Structure):
+    """pgn_ctc_params"""
+    _fields_ = [("classes", C.c_uint32), ("blank", C.c_uint32), ("score_type", C.c_uint32), ("pad", C.c_uint32),
+                ("alphabet", C.c_uint8 * 64)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -159,6 +168,12 @@ SIGNATURES = [
     ("pgn_stitch_rows_device", C.c_int,
      [_VP, C.POINTER(StitchParams), _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, C.c_uint64, C.c_uint32, _VP,
       C.c_uint64, C.c_uint64, _VP]),
+    ("pgn_ctc_decode_device", C.c_int,
+     [_VP, C.POINTER(CtcParams), _SZ, _U64P, _VP, C.c_uint64, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _U64P, _I32P,
+      _U32P, _VP, _VP, _VP]),
+    ("pgn_collapse_codes_device", C.c_int,
+     [_VP, C.POINTER(C.c_uint8 * 128), _SZ, _U64P, _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _U64P, _I32P, _U32P,
+      _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

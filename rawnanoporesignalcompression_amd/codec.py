@@ -26,7 +26,9 @@ quantiles or median / MAD; :meth:`PGNanoCodec.read_stats` gives those statistics
 ``[segments, length]`` tensor a model reads (:func:`trim_signal` and :func:`segment_signal` on the host).
 :meth:`PGNanoCodec.stitch_plan` and :meth:`PGNanoCodec.stitch` undo that cut for the model's output: they drop
 the frames doubled where rows overlap and lay each read's frames end to end (:func:`stitch_plan_signal` on the
-host).
+host).  :meth:`PGNanoCodec.ctc_decode` turns those frames into bases by the best-path CTC rule, and
+:meth:`PGNanoCodec.collapse_codes` is its second half for per-frame codes of any source
+(:func:`ctc_decode_signal` and :func:`collapse_codes_signal` on the host).
 """
 from __future__ import annotations
 
@@ -362,6 +364,80 @@ def stitch_bound(counts, length, overlap, frame_samples) -> int:
     p = stitch_params(length, overlap, frame_samples)
     n = np.asarray(counts).astype(np.int64).reshape(-1)
     return int((-(-n // p.frame_samples)).sum()) + segment_bound(n, p.length, p.overlap)
+
+
+@dataclass
+class DecodedReads:
+    """What :meth:`PGNanoCodec.ctc_decode` and :meth:`PGNanoCodec.collapse_codes` leave on the device."""
+    seq: "object"         # uint8, capacity: read r's bases are seq[read_bases[r]:read_bases[r + 1]]; the entries
+                          # of seq, base_frame and base_score from read_bases[-1] on are not initialised, nor are
+                          # the codes of frames outside the taken reads
+    read_bases: "object"  # int64, reads + 1: the full counts, also where the capacity cut the bases
+    status: "object"      # int32 per read: 0, PGN_ERR_DST_TOO_SMALL (1) or PGN_ERR_INVALID_ARG (10, not taken)
+    base_frame: "object"  # int32 per base (the uint32's bits): its frame within the read; or None
+    base_score: "object"  # float32 per base: the winning score of its frame; or None
+    codes: "object"       # uint8 per frame of the window: label, bit 7 set where the frame emits; or None
+    params: "object"      # the pgn_ctc_params of a decode, the 128-entry alphabet of a collapse
+
+    def sequences(self):
+        """One ``bytes`` per read (waits on the host); a read the capacity cut gives the bases that fit."""
+        seq, rb = self.seq.cpu().numpy(), self.read_bases.cpu().numpy()
+        return [seq[a:b].tobytes() for a, b in zip(rb[:-1], rb[1:])]
+
+
+def _alphabet_bytes(alphabet, entries):
+    a = alphabet.encode("latin-1") if isinstance(alphabet, str) else bytes(bytearray(alphabet))
+    if len(a) > entries:
+        raise ValueError(f"alphabet has {len(a)} entries, at most {entries} fit")
+    return a
+
+
+def ctc_params(classes, blank=0, alphabet="NACGT", dtype=np.float16):
+    """``pgn_ctc_params``: ``classes`` scores per frame (2..64) of ``dtype`` (float16 or float32), class
+    ``blank`` emits nothing, class ``c`` writes ``alphabet[c]`` (one byte per class)."""
+    C_, blank = int(classes), int(blank)
+    a = _alphabet_bytes(alphabet, 64)
+    types = {np.dtype(np.float32): _native.PGN_OUT_F32, np.dtype(np.float16): _native.PGN_OUT_F16}
+    if not (2 <= C_ <= 64 and 0 <= blank < C_):
+        raise ValueError(f"need 2 <= classes <= 64 and 0 <= blank < classes (got {C_}, {blank})")
+    if len(a) != C_:
+        raise ValueError(f"alphabet must have one entry per class ({C_}), got {len(a)}")
+    if np.dtype(dtype) not in types:
+        raise ValueError("scores must be float16 or float32")
+    return _native.CtcParams(C_, blank, types[np.dtype(dtype)], 0, (C.c_uint8 * 64)(*a))
+
+
+def collapse_codes_signal(codes, alphabet):
+    """The bases of one read's code bytes on the host (include/pgnano_hip.h, "Stitched frames to bases"): a
+    frame emits iff bit 7 of its code is set, and its base is ``alphabet[code & 0x7f]``.  Returns ``(seq,
+    base_frame)``: uint8 bases and the uint32 frame of each."""
+    codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+    table = np.zeros(128, np.uint8)
+    a = _alphabet_bytes(alphabet, 128)
+    table[:len(a)] = np.frombuffer(a, np.uint8)
+    at = np.flatnonzero(codes & 0x80)
+    return table[codes[at] & 0x7F], at.astype(np.uint32)
+
+
+def ctc_decode_signal(scores, alphabet="NACGT", blank=0):
+    """The best-path CTC decode of one read's ``[frames, classes]`` scores on the host (include/pgnano_hip.h,
+    "Stitched frames to bases"): the label of a frame is ``np.argmax`` of its scores, a frame emits iff its
+    label is not ``blank`` and it is the read's first frame or its label differs from the frame before.
+    Returns ``(seq, base_frame, base_score, codes)``: uint8 bases, the uint32 frame and the float32 winning
+    score of each, and one code byte per frame (the label, bit 7 set where the frame emits).
+    :meth:`PGNanoCodec.ctc_decode` writes these values for a read that is taken."""
+    scores = np.asarray(scores)
+    if scores.ndim != 2:
+        raise ValueError("scores must be [frames, classes]")
+    prm = ctc_params(scores.shape[1], blank, alphabet, scores.dtype)
+    if scores.shape[0] == 0:
+        return np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, np.uint8)
+    labels = np.argmax(scores, axis=1)
+    emit = labels != prm.blank
+    emit[1:] &= labels[1:] != labels[:-1]
+    codes = (labels | np.where(emit, 0x80, 0)).astype(np.uint8)
+    seq, at = collapse_codes_signal(codes, bytes(prm.alphabet))
+    return seq, at, scores[at, labels[at]].astype(np.float32), codes
 
 
 @dataclass
@@ -828,6 +904,88 @@ class PGNanoCodec:
                 int(rows.stride(td)) * item, frame_bytes, _ptr(out), frame_base, int(out.shape[0]), ls.cuda_stream))
         caller.wait_stream(ls)
         return out
+
+    def _decode_outputs(self, read_frames, frames, capacity, base_frame, dev):
+        """The arguments both base calls share, checked, and their output tensors (on the launch stream)."""
+        import torch
+
+        _require_device(read_frames, "read_frames", self.device)
+        if read_frames.dtype != torch.int64 or read_frames.dim() != 1 or read_frames.numel() < 1 or not read_frames.is_contiguous():
+            raise ValueError("read_frames must be a contiguous int64 tensor of reads + 1 offsets")
+        capacity = frames if capacity is None else int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        n = int(read_frames.numel()) - 1
+        seq = torch.empty(capacity, dtype=torch.uint8, device=dev)
+        bases = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        bf = torch.empty(capacity, dtype=torch.int32, device=dev) if base_frame else None
+        return n, capacity, seq, bases, status, bf
+
+    def ctc_decode(self, frames, read_frames, *, alphabet="NACGT", blank=0, frame_base: int = 0, capacity=None,
+                   base_frame: bool = True, base_score: bool = True, codes: bool = False,
+                   stream: int | None = None) -> DecodedReads:
+        """The best-path CTC decode of stitched frames (pgn_ctc_decode_device): per read
+        :func:`ctc_decode_signal` of its frames.
+
+        frames: ``[F, C]`` float16 or float32, the last dimension contiguous, the first of any stride that is at
+        least the frame; ``frames[i - frame_base]`` is frame ``i`` of the layout ``read_frames`` (int64, reads +
+        1, as :meth:`stitch_plan` leaves it) describes.  A read that does not lie wholly in ``[frame_base,
+        frame_base + F)`` gets status 10 and no bases.  capacity: the bases ``seq`` holds (default ``F``, which
+        always suffices); reads cut by it get status 1, and ``read_bases`` still holds the full counts.
+        ``base_frame`` / ``base_score`` / ``codes``: whether those outputs are made.  No host wait."""
+        import torch
+
+        _require_device(frames, "frames", self.device)
+        if frames.dim() != 2 or frames.dtype not in (torch.float16, torch.float32):
+            raise ValueError("frames must be a [F, C] tensor of float16 or float32")
+        F, C_ = int(frames.shape[0]), int(frames.shape[1])
+        prm = ctc_params(C_, blank, alphabet, np.float16 if frames.dtype == torch.float16 else np.float32)
+        if frames.stride(1) != 1 or (F > 1 and frames.stride(0) < C_):
+            raise ValueError("the last dimension of frames must be contiguous and the first stride at least C")
+        frame_base = int(frame_base)
+        if not 0 <= frame_base < 1 << 62:
+            raise ValueError("frame_base must lie in [0, 2^62)")
+        item = frames.element_size()
+        stride = max(int(frames.stride(0)), C_) * item
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            dev = frames.device
+            n, capacity, seq, bases, status, bf = self._decode_outputs(read_frames, F, capacity, base_frame, dev)
+            bs = torch.empty(capacity, dtype=torch.float32, device=dev) if base_score else None
+            cd = torch.empty(F, dtype=torch.uint8, device=dev) if codes else None
+            _check(self._lib.pgn_ctc_decode_device(
+                self._h, C.byref(prm), n, _ptr(read_frames), _ptr(frames) if F else 0, stride, frame_base, F, _ptr(seq),
+                capacity, _ptr(bases), _ptr(status), _ptr(bf), _ptr(bs), _ptr(cd), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return DecodedReads(seq, bases, status, bf, bs, cd, prm)
+
+    def collapse_codes(self, codes, read_frames, alphabet, *, frame_base: int = 0, capacity=None,
+                       base_frame: bool = True, stream: int | None = None) -> DecodedReads:
+        """Code bytes to bases (pgn_collapse_codes_device), the second half of :meth:`ctc_decode` for codes of any
+        source: per read :func:`collapse_codes_signal` of its codes.  codes: uint8, contiguous, ``codes[i -
+        frame_base]`` for frame ``i``; alphabet: up to 128 bytes, the base of class ``code & 0x7f``.  The
+        window, ``capacity`` and the statuses are those of :meth:`ctc_decode`.  No host wait."""
+        import torch
+
+        _require_device(codes, "codes", self.device)
+        if codes.dtype != torch.uint8 or codes.dim() != 1 or not codes.is_contiguous():
+            raise ValueError("codes must be a contiguous one-dimensional uint8 tensor")
+        table = (C.c_uint8 * 128)(*_alphabet_bytes(alphabet, 128))
+        frame_base, F = int(frame_base), int(codes.numel())
+        if not 0 <= frame_base < 1 << 62:
+            raise ValueError("frame_base must lie in [0, 2^62)")
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            n, capacity, seq, bases, status, bf = self._decode_outputs(read_frames, F, capacity, base_frame,
+                                                                       codes.device)
+            _check(self._lib.pgn_collapse_codes_device(
+                self._h, C.byref(table), n, _ptr(read_frames), _ptr(codes) if F else 0, frame_base, F, _ptr(seq), capacity,
+                _ptr(bases), _ptr(status), _ptr(bf), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return DecodedReads(seq, bases, status, bf, None, codes, table)
 
     def decompress_reads_norm(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, *,
                               mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0,

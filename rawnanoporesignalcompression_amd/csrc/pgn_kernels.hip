@@ -20,6 +20,7 @@
 #include "pgn_internal.h"
 #include "pgn_segment.h"
 #include "pgn_stitch.h"
+#include "pgn_ctc.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2126,6 +2127,12 @@ struct pgn_ctx {
     // pgn_stitch_plan_device: the frame totals of the count kernel's workgroups, then their sum
     uint64_t* stitchSums = nullptr;
     size_t stitchBlocks = 0;
+    // pgn_ctc_decode_device / pgn_collapse_codes_device: the tiles' base counts, the reads at the tile edges
+    // and the spans' sums with the total, in one block; the code bytes of a decode whose caller passes no array
+    uint64_t* ctcSums = nullptr;
+    size_t ctcTiles = 0;
+    uint8_t* ctcCodes = nullptr;
+    size_t ctcCodeBytes = 0;
     // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
     // first work items and the slots in one block sized by max_split_reads; the per-read counts the one-workgroup kernel reads.
     // Defaults measured by tools/select_split_timing.py (profiles/select_split_timing.log)
@@ -2326,6 +2333,8 @@ int pgn_ctx_destroy(pgn_ctx* c)
     (void)hipFree(c->normStats);
     (void)hipFree(c->segWork);
     (void)hipFree(c->stitchSums);
+    (void)hipFree(c->ctcSums);
+    (void)hipFree(c->ctcCodes);
     (void)hipFree(c->splitWork);
     (void)hipFree(c->splitWholeCounts);
     if (c->largeHdrHost) (void)hipHostFree(c->largeHdrHost);
@@ -3805,6 +3814,140 @@ extern "C" int pgn_stitch_rows_device(pgn_ctx* c, const pgn_stitch_params* param
     HIPCHK(hipEventRecord(c->evLast, s));
     c->haveLast = true;
     return PGN_OK;
+}
+
+// ---- stitched frames to bases (pgn_ctc.h) -----------------------------------------------------------
+static int ensure_ctc(pgn_ctx* c, size_t ntiles, size_t codeBytes)
+{
+    if (ntiles > c->ctcTiles) {
+        wait_last_host(c);
+        (void)hipFree(c->ctcSums);
+        c->ctcSums = nullptr;
+        c->ctcTiles = 0;
+        // the tiles' sums, the edges' reads, the spans' sums and the total
+        HIPCHK(hipMalloc(&c->ctcSums, ((ntiles + 1) * 2 + ntiles / ctc::kScanSpan + 2) * sizeof(uint64_t)));
+        c->ctcTiles = ntiles;
+    }
+    if (codeBytes > c->ctcCodeBytes) {
+        wait_last_host(c);
+        (void)hipFree(c->ctcCodes);
+        c->ctcCodes = nullptr;
+        c->ctcCodeBytes = 0;
+        HIPCHK(hipMalloc(&c->ctcCodes, codeBytes));
+        c->ctcCodeBytes = codeBytes;
+    }
+    return PGN_OK;
+}
+
+// what the two calls share once their arguments are checked: the label pass (decode) or the count of the
+// caller's codes (collapse), the scan, the write pass and the statuses
+static int ctc_run(pgn_ctx* c, ctc::Args& a, bool decode, bool ownCodes, void* stream)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    if (a.nreads == 0) {
+        HIPCHK(hipMemsetAsync(a.readBases, 0, sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    if (a.capacity > UINT64_MAX - a.frameBase) a.capacity = UINT64_MAX - a.frameBase;  // no frame index wraps
+    a.ntiles = std::max<uint64_t>(1, (a.capacity + ctc::kTile - 1) / ctc::kTile);
+    const int rc = ensure_ctc(c, (size_t)a.ntiles, ownCodes ? (size_t)a.capacity : 0);
+    if (rc != PGN_OK) return rc;
+    a.tileSums = c->ctcSums;
+    a.bounds = reinterpret_cast<uint32_t*>(c->ctcSums + c->ctcTiles + 1);
+    a.spanSums = c->ctcSums + 2 * (c->ctcTiles + 1);
+    a.nspans = (a.ntiles + ctc::kScanSpan - 1) / ctc::kScanSpan;
+    if (ownCodes) a.codes = c->ctcCodes;
+    const dim3 grid((unsigned)a.ntiles), block(ctc::kThreads);
+    const size_t stageBytes = a.staged ? (size_t)ctc::kTile * a.classes * a.elem + 16 : 0;
+    hipLaunchKernelGGL(ctc::ctc_bounds_kernel, dim3((unsigned)(a.ntiles / 256 + 1)), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (decode)
+        hipLaunchKernelGGL(ctc::ctc_label_kernel, grid, block, stageBytes, s, a);
+    else
+        hipLaunchKernelGGL(ctc::ctc_count_kernel, grid, block, 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ctc::ctc_scan_kernel, dim3((unsigned)a.nspans), dim3(ctc::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    stitch::PlanArgs top{};  // the scan of the spans' totals is the stitch plan's
+    top.blockSums = a.spanSums;
+    top.nblocks = a.nspans;
+    hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, top);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ctc::ctc_write_kernel, grid, block, 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ctc::ctc_status_kernel, dim3((unsigned)(a.nreads / 256 + 1)), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->evLast, s));
+    c->haveLast = true;
+    return PGN_OK;
+}
+
+extern "C" int pgn_ctc_decode_device(pgn_ctx* c, const pgn_ctc_params* params, size_t nreads,
+                                     const uint64_t* d_read_frames, const void* d_frames, uint64_t frame_stride_bytes,
+                                     uint64_t frame_base, uint64_t frame_capacity, uint8_t* d_seq, uint64_t base_capacity,
+                                     uint64_t* d_read_bases, int32_t* d_read_status, uint32_t* d_base_frame,
+                                     float* d_base_score, uint8_t* d_codes, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!ctc::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    const uint32_t elem = ctc::elem_bytes(params->score_type);
+    const uint64_t frameBytes = (uint64_t)params->classes * elem;
+    if (frame_stride_bytes < frameBytes || frame_stride_bytes % elem || (uintptr_t)d_frames % elem) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32 || frame_capacity >> 40) return PGN_ERR_INVALID_ARG;
+    if (!d_read_bases) return PGN_ERR_INVALID_ARG;
+    if (nreads && (!d_read_frames || !d_read_status)) return PGN_ERR_INVALID_ARG;
+    if (frame_capacity && !d_frames) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && !d_seq) return PGN_ERR_INVALID_ARG;
+    ctc::Args a{};
+    a.nreads = nreads;
+    a.readFrames = d_read_frames;
+    a.frames = static_cast<const uint8_t*>(d_frames);
+    a.frameStride = frame_stride_bytes;
+    a.classes = params->classes;
+    a.blank = params->blank;
+    a.elem = elem;
+    a.staged = frame_stride_bytes == frameBytes && frameBytes <= ctc::kStageFrameBytes;
+    a.frameBase = frame_base;
+    a.capacity = frame_capacity;
+    a.codes = d_codes;
+    a.seq = d_seq;
+    a.baseCapacity = base_capacity;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.baseFrame = d_base_frame;
+    a.baseScore = d_base_score;
+    memcpy(a.alphabet, params->alphabet, sizeof params->alphabet);
+    return ctc_run(c, a, true, d_codes == nullptr, stream);
+}
+
+extern "C" int pgn_collapse_codes_device(pgn_ctx* c, const uint8_t alphabet[128], size_t nreads,
+                                         const uint64_t* d_read_frames, const uint8_t* d_codes, uint64_t frame_base,
+                                         uint64_t frame_capacity, uint8_t* d_seq, uint64_t base_capacity,
+                                         uint64_t* d_read_bases, int32_t* d_read_status, uint32_t* d_base_frame,
+                                         void* stream)
+{
+    if (!c || !alphabet) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32 || frame_capacity >> 40) return PGN_ERR_INVALID_ARG;
+    if (!d_read_bases) return PGN_ERR_INVALID_ARG;
+    if (nreads && (!d_read_frames || !d_read_status)) return PGN_ERR_INVALID_ARG;
+    if (frame_capacity && !d_codes) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && !d_seq) return PGN_ERR_INVALID_ARG;
+    ctc::Args a{};
+    a.nreads = nreads;
+    a.readFrames = d_read_frames;
+    a.frameBase = frame_base;
+    a.capacity = frame_capacity;
+    a.codes = const_cast<uint8_t*>(d_codes);  // the count and the write pass only read them
+    a.seq = d_seq;
+    a.baseCapacity = base_capacity;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.baseFrame = d_base_frame;
+    memcpy(a.alphabet, alphabet, sizeof a.alphabet);
+    return ctc_run(c, a, false, false, stream);
 }
 
 // ---- in-library entry points of the POD5 loader (pgn_internal.h) --------------------------------
