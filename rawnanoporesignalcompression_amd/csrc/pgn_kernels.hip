@@ -2005,7 +2005,23 @@ struct PcArena {
     int state = 0;            // 0 idle / open, 1 on the device, 2 results being copied out
 };
 
+// A grow-only device allocation of a context: the pointer and its capacity in bytes.  It can only be
+// constructed into its owner's list, which is what pgn_ctx_destroy frees; reserve() is what grows it.
+struct DevMem {
+    void* p = nullptr;
+    size_t cap = 0;
+    explicit DevMem(std::vector<DevMem*>& owner) { owner.push_back(this); }
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+};
+template <class T>
+struct DevBuf : DevMem {
+    using DevMem::DevMem;
+    operator T*() const { return static_cast<T*>(p); }
+};
+
 struct pgn_ctx {
+    std::vector<DevMem*> bufs;  // every DevBuf below (declared first: they register as they are constructed)
     int device = 0;
     hipStream_t stream = nullptr;
     int numCUs = 0;
@@ -2031,36 +2047,28 @@ struct pgn_ctx {
     // A deferred pass ends with one lane's ~16,000-symbol chain per M stream, which nothing overlaps
     // once the frame decode of the last pass is done (the decode's drain)
     size_t deferTailPlain = 0;
-    size_t deferHead = 0;      // PGN_DEFER_HEAD: chunks of a short first deferred pass (0 = balanced passes)
     bool hufPrioLast = false;  // PGN_HUF_PRIO_LAST=1: the last deferred pass's dec_huf waves at raised priority
-    bool lastOnCaller = false;  // PGN_LAST_ON_CALLER=1: the last deferred pass's sections and merge on the caller's stream
     size_t hufWideLast = 0;    // PGN_HUF_WIDE_LAST: the last this many deferred passes decode their sections with dec_huf_wide_kernel
     bool lastDeferred = false;  // the last staged C5 decode deferred its Huffman sections (pgn_ctx_kernels)
     // encode: per-slot scratch of the zstd kernel, per-chunk streams/frames of one sub-batch
-    uint8_t* encScratch = nullptr;
-    size_t encSlots = 0;
-    uint32_t* epochs = nullptr;
-    uint8_t* encChunks = nullptr;  // per buffer: G * (kChunkStreamBytes + kChunkFrameBytes) + sizes + fsizes
-    size_t encG = 0;               // chunk capacity of all buffers together
+    DevBuf<uint8_t> encScratch{bufs};
+    DevBuf<uint32_t> epochs{bufs};
+    DevBuf<uint8_t> encChunks{bufs};  // per buffer: G * (kChunkStreamBytes + kChunkFrameBytes) + sizes + fsizes
     // decode
-    uint8_t* decScratch = nullptr;
-    size_t decSlots = 0;
-    uint8_t* decChunks = nullptr;  // per buffer: G * interStride + units (+ Huffman jobs)
-    size_t decBytes = 0;
+    DevBuf<uint8_t> decScratch{bufs};
+    DevBuf<uint8_t> decChunks{bufs};  // per buffer: G * interStride + units (+ Huffman jobs)
     DecUnit* lastUnits = nullptr;  // decode records of the last pass (diagnostics)
     size_t lastG = 0;              // ... for this many chunks
-    uint32_t* queues = nullptr;    // a ring of work counters, zeroed when it wraps (one per sub-batch pass)
+    DevBuf<uint32_t> queues{bufs};  // a ring of work counters, zeroed when it wraps (one per sub-batch pass)
     size_t qNext = 0;              // next unused counter of the ring
     uint32_t* qCur = nullptr;      // the current call's counters
-    uint64_t* lookback = nullptr;  // dec_merge_lb_kernel's published words (kMergeWgMaxChunks chunks)
+    DevBuf<uint64_t> lookback{bufs};  // dec_merge_lb_kernel's published words (kMergeWgMaxChunks chunks)
     uint64_t lbEpoch = 0;          // the tag of the last call that used them
-    size_t nQueues = 0;
     // host-call staging: a device buffer and its pinned host mirror (same layout), so a per-chunk
     // call is one upload, the launches and one download
-    uint8_t* stage = nullptr;
-    uint8_t* hstage = nullptr;
+    DevBuf<uint8_t> stage{bufs};
+    uint8_t* hstage = nullptr;     // as large as stage (null: to be allocated)
     uint8_t* hstageDev = nullptr;  // the device's address of hstage (kernels write the call's outputs there)
-    size_t stageBytes = 0;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // two-stream pipeline over sub-batches (launch_encode / launch_decode): the side stream runs the
     // split (encode) or the merge (decode) of one sub-batch while the caller's stream runs the zstd
@@ -2070,7 +2078,6 @@ struct pgn_ctx {
     // deferred-Huffman decode passes: the merges on a third stream, so the merge of pass p (VALU-bound)
     // can share the CUs with the Huffman sections of pass p + 1 (latency-bound)
     hipStream_t mergeS = nullptr;
-    hipEvent_t evHuf[2] = {nullptr, nullptr};
     // decode passes: buffers in rotation (PGN_DEC_BUFS, 2..kMaxDecBufs) with their stage / sections /
     // free events, and the streams the deferred sections alternate over (PGN_HUF_STREAMS: 1 or 2 with
     // the merges on mergeS; 3 = sections and merge of pass p both on side stream p % 3 of side, side2,
@@ -2080,67 +2087,55 @@ struct pgn_ctx {
     size_t decBufs = 4, hufStreams = 3;
     hipStream_t side2 = nullptr;
     hipEvent_t evDStage[kMaxDecBufs] = {}, evDHuf[kMaxDecBufs] = {}, evDFree[kMaxDecBufs] = {};
-    uint64_t* prof = nullptr;  // kProfWords: phase cycles and counters (encode, decode, dec_huf) when PGN_PHASE_PROFILE=1
+    DevBuf<uint64_t> prof{bufs};  // kProfWords: phase cycles and counters (encode, decode, dec_huf) when PGN_PHASE_PROFILE=1
     bool encTimed = false, decTimed = false;
     // Stream ordering of the context's shared state (work counters, slot scratch, per-chunk buffers):
     // every launch sequence records evLast on its stream at the end, and the next one, on whatever
-    // stream, waits for it before touching that state.  Calls on one context therefore run in call
-    // order on the device even when callers pass different streams.
+    // stream, waits for it before touching that state (CallScope).  Calls on one context therefore run
+    // in call order on the device even when callers pass different streams.
     hipEvent_t evLast = nullptr;
     bool haveLast = false;
     // Large-chunk pass (chunks above kPassSamples, launch_large): the chunk list, its header
     // {count, largest} on the device and in pinned memory, read on a stream of its own while the
     // batched pass runs; slot scratch spaced for the largest chunk, and its own table epochs and
     // work counter.
-    uint32_t* largeList = nullptr;
-    uint32_t* claimList = nullptr;     // the claims pass's chunks (claim_scan_kernel, or from the host)
-    size_t largeListCap = 0;
-    uint32_t* largeHdr = nullptr;      // [0..1] header, [2] the large pass's work counter, [3] largest chunk,
+    DevBuf<uint32_t> largeList{bufs};
+    DevBuf<uint32_t> claimList{bufs};  // the claims pass's chunks (claim_scan_kernel, or from the host)
+    DevBuf<uint32_t> largeHdr{bufs};   // [0..1] header, [2] the large pass's work counter, [3] largest chunk,
                                        // [4..5] the claims pass's count and largest sum (KiB)
     uint32_t* largeHdrHost = nullptr;
     hipStream_t scanStream = nullptr;
     hipEvent_t evScanFork = nullptr, evScan = nullptr;
     // the encode and the decode of the large pass keep separate slot scratch: the encoder's hash
     // tables persist across calls (epoch tags), so a decode must never write over them
-    uint8_t* largeScratch = nullptr;
-    size_t largeScratchBytes = 0;
-    uint32_t* largeEpochs = nullptr;
-    size_t largeEpochSlots = 0;
-    uint8_t* largeDecScratch = nullptr;
-    size_t largeDecScratchBytes = 0;
+    DevBuf<uint8_t> largeScratch{bufs};
+    DevBuf<uint32_t> largeEpochs{bufs};
+    DevBuf<uint8_t> largeDecScratch{bufs};
     // pgn_decompress_reads_device_norm: the reads expanded to chunks (per chunk: output offset and
     // read; per read: n and, when the caller passes no d_stats, the statistics)
-    uint64_t* normChunkOut = nullptr;
-    uint32_t* normChunkRead = nullptr;
-    uint64_t* normReadN = nullptr;
-    pgn_read_stats* normStats = nullptr;
-    size_t normChunks = 0, normReads = 0;
+    DevBuf<uint64_t> normChunkOut{bufs};
+    DevBuf<uint32_t> normChunkRead{bufs};
+    DevBuf<uint64_t> normReadN{bufs};
+    DevBuf<pgn_read_stats> normStats{bufs};
     // pgn_decompress_reads_device_pa: the reads' calibration expanded to chunks (the chunks' output
     // offsets share normChunkOut)
-    float* paChunkOffset = nullptr;
-    float* paChunkScale = nullptr;
-    size_t paChunks = 0;
+    DevBuf<float> paChunkOffset{bufs};
+    DevBuf<float> paChunkScale{bufs};
     // pgn_segment_reads_device: per read the head count, the trimmed offset and count, the head's and the
     // trimmed read's statistics; then the segment total (one block, carved up by ensure_segment)
-    uint8_t* segWork = nullptr;
-    size_t segReads = 0;
+    DevBuf<uint8_t> segWork{bufs};
     // pgn_stitch_plan_device: the frame totals of the count kernel's workgroups, then their sum
-    uint64_t* stitchSums = nullptr;
-    size_t stitchBlocks = 0;
+    DevBuf<uint64_t> stitchSums{bufs};
     // pgn_ctc_decode_device / pgn_collapse_codes_device: the tiles' base counts, the reads at the tile edges
     // and the spans' sums with the total, in one block; the code bytes of a decode whose caller passes no array
-    uint64_t* ctcSums = nullptr;
-    size_t ctcTiles = 0;
-    uint8_t* ctcCodes = nullptr;
-    size_t ctcCodeBytes = 0;
+    DevBuf<uint64_t> ctcSums{bufs};
+    DevBuf<uint8_t> ctcCodes{bufs};
     // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
     // first work items and the slots in one block sized by max_split_reads; the per-read counts the one-workgroup kernel reads.
     // Defaults measured by tools/select_split_timing.py (profiles/select_split_timing.log)
     pgn_select_split split = {196608u, 32768u, 1024u, 0u};
-    uint8_t* splitWork = nullptr;
-    size_t splitSlots = 0;
-    uint64_t* splitWholeCounts = nullptr;
-    size_t splitReads = 0;
+    DevBuf<uint8_t> splitWork{bufs};
+    DevBuf<uint64_t> splitWholeCounts{bufs};
     bool splitCounted = false;  // the last selection ran the plan kernel (pgn_select_split_counts)
     // an object of another translation unit (the POD5 loader's staging, pgn_internal.h)
     void* ext = nullptr;
@@ -2198,15 +2193,19 @@ size_t pgn_compressed_signal_max_size(size_t n)
     return s > 1024 ? s : 1024;
 }
 
-int pgn_ctx_create(int device, pgn_ctx** out)
+// An empty buffer's first allocation (the fixed-size ones; the others grow through reserve()).
+static hipError_t dev_alloc(DevMem& b, size_t bytes)
 {
-    if (!out) return PGN_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PGN_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return PGN_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(device));
-    pgn_ctx* c = new pgn_ctx();
-    c->device = device;
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e == hipSuccess) b.cap = bytes;
+    return e;
+}
+
+// The settings, streams, events and fixed-size buffers of a new context (c->device is set and current).
+// On an error pgn_ctx_create destroys what exists by then.
+static int ctx_init(pgn_ctx* c)
+{
+    const int device = c->device;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     c->numCUs = prop.multiProcessorCount;
@@ -2243,8 +2242,6 @@ int pgn_ctx_create(int device, pgn_ctx** out)
     }
     if (const char* v = getenv("PGN_DEFER_MIN_CHUNKS")) { const long x = atol(v); if (x > 0) c->deferMin = (size_t)x; }
     if (const char* v = getenv("PGN_DEFER_G")) { const long x = atol(v); if (x > 0) c->deferG = (size_t)x; }
-    if (const char* v = getenv("PGN_DEFER_HEAD")) { const long x = atol(v); if (x >= 0) c->deferHead = (size_t)x; }
-    if (const char* v = getenv("PGN_LAST_ON_CALLER")) c->lastOnCaller = v[0] == '1';
     if (const char* v = getenv("PGN_HUF_WIDE_LAST")) { const long x = atol(v); if (x >= 0) c->hufWideLast = (size_t)x; }
     if (const char* v = getenv("PGN_HUF_PRIO_LAST")) c->hufPrioLast = v[0] == '1';
     if (const char* v = getenv("PGN_DEFER_TAIL_PLAIN")) { const long x = atol(v); if (x >= 0) c->deferTailPlain = (size_t)x; }
@@ -2252,7 +2249,7 @@ int pgn_ctx_create(int device, pgn_ctx** out)
     const char* pe = getenv("PGN_PHASE_PROFILE");
     if (pe && pe[0] == '1') {
         // [encode phases][decode phases][encode counters][decode counters]
-        HIPCHK(hipMalloc(&c->prof, kProfWords * sizeof(uint64_t)));
+        HIPCHK(dev_alloc(c->prof, kProfWords * sizeof(uint64_t)));
         HIPCHK(hipMemset(c->prof, 0, kProfWords * sizeof(uint64_t)));
         HIPCHK(hipDeviceSynchronize());
     }
@@ -2277,14 +2274,13 @@ int pgn_ctx_create(int device, pgn_ctx** out)
     HIPCHK(hipStreamCreateWithFlags(&c->scanStream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->evScanFork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->evScan, hipEventDisableTiming));
-    HIPCHK(hipMalloc(&c->largeHdr, 8 * sizeof(uint32_t)));
+    HIPCHK(dev_alloc(c->largeHdr, 8 * sizeof(uint32_t)));
     HIPCHK(hipHostMalloc((void**)&c->largeHdrHost, 8 * sizeof(uint32_t), hipHostMallocDefault));
     HIPCHK(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming));
     for (int i = 0; i < 2; i++) {
         HIPCHK(hipEventCreateWithFlags(&c->evStage[i], hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&c->evFree[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->evHuf[i], hipEventDisableTiming));
     }
     // the predefined sequence FSE tables of the decoder (one wave, once per context)
     hipLaunchKernelGGL(seq_default_tables_kernel, dim3(1), dim3(64), 0, c->stream);
@@ -2293,50 +2289,42 @@ int pgn_ctx_create(int device, pgn_ctx** out)
     hipLaunchKernelGGL(seq_default_ctables_kernel, dim3(1), dim3(64), 0, c->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
+    return PGN_OK;
+}
+
+int pgn_ctx_create(int device, pgn_ctx** out)
+{
+    if (!out) return PGN_ERR_INVALID_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PGN_ERR_NO_DEVICE;
+    if (device < 0 || device >= ndev) return PGN_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    pgn_ctx* c = new pgn_ctx();
+    c->device = device;
+    const int rc = ctx_init(c);
+    if (rc != PGN_OK) {  // whatever step failed: nothing of the context is left, *out is untouched
+        (void)pgn_ctx_destroy(c);
+        return rc;
+    }
     *out = c;
     return PGN_OK;
 }
 
+// Also the teardown of a context whose creation failed part-way: every member may still be null.
 int pgn_ctx_destroy(pgn_ctx* c)
 {
     if (!c) return PGN_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->haveLast) (void)hipEventSynchronize(c->evLast);
     if (c->ext && c->extDestroy) c->extDestroy(c->ext);
-    (void)hipFree(c->paChunkOffset);
-    (void)hipFree(c->paChunkScale);
-    (void)hipFree(c->encScratch);
-    (void)hipFree(c->epochs);
-    (void)hipFree(c->decScratch);
-    (void)hipFree(c->encChunks);
-    (void)hipFree(c->decChunks);
-    (void)hipFree(c->queues);
-    (void)hipFree(c->lookback);
-    (void)hipFree(c->stage);
+    if (c->scanStream) (void)hipStreamSynchronize(c->scanStream);
+    for (DevMem* b : c->bufs) (void)hipFree(b->p);
     if (c->hstage) (void)hipHostFree(c->hstage);
-    (void)hipFree(c->prof);
     for (PcArena& A : c->pcA) {
         if (A.h) (void)hipHostFree(A.h);
         (void)hipFree(A.d);
     }
-    if (c->scanStream) (void)hipStreamSynchronize(c->scanStream);
-    (void)hipFree(c->largeList);
-    (void)hipFree(c->claimList);
-    (void)hipFree(c->largeHdr);
-    (void)hipFree(c->largeScratch);
-    (void)hipFree(c->largeEpochs);
-    (void)hipFree(c->largeDecScratch);
-    (void)hipFree(c->normChunkOut);
-    (void)hipFree(c->normChunkRead);
-    (void)hipFree(c->normReadN);
-    (void)hipFree(c->normStats);
-    (void)hipFree(c->segWork);
-    (void)hipFree(c->stitchSums);
-    (void)hipFree(c->ctcSums);
-    (void)hipFree(c->ctcCodes);
-    (void)hipFree(c->splitWork);
-    (void)hipFree(c->splitWholeCounts);
     if (c->largeHdrHost) (void)hipHostFree(c->largeHdrHost);
     for (hipEvent_t e : {c->evScanFork, c->evScan})
         if (e) (void)hipEventDestroy(e);
@@ -2349,13 +2337,12 @@ int pgn_ctx_destroy(pgn_ctx* c)
         for (hipEvent_t e : {c->evDStage[i], c->evDHuf[i], c->evDFree[i]})
             if (e) (void)hipEventDestroy(e);
     if (c->evLast) (void)hipEventSynchronize(c->evLast);
-    for (hipEvent_t e : {c->evFork, c->evJoin, c->evStage[0], c->evStage[1], c->evFree[0], c->evFree[1], c->evLast, c->evHuf[0],
-                         c->evHuf[1]})
+    for (hipEvent_t e : {c->evFork, c->evJoin, c->evStage[0], c->evStage[1], c->evFree[0], c->evFree[1], c->evLast})
         if (e) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->mergeS) (void)hipStreamDestroy(c->mergeS);
     if (c->side2) (void)hipStreamDestroy(c->side2);
-    (void)hipStreamDestroy(c->stream);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return PGN_OK;
 }
@@ -2369,53 +2356,86 @@ static void wait_last_host(pgn_ctx* c)
     (void)hipStreamSynchronize(c->stream);
 }
 
-static int ensure_enc(pgn_ctx* c, size_t slots, size_t G)
+// The one place a context's scratch grows.  `group` lists buffers that are sized together with the bytes
+// each must hold: when any of them is too small, all are freed and allocated again at exactly the bytes
+// asked for (no geometric growth).  Before anything is freed the host waits for the last launch sequence,
+// and, by `flags`, for the whole device, for the scan stream or for `also`, the caller's stream.  kZeroFill
+// clears the new memory on the context's stream and waits for that (the stream is non-blocking, so a
+// launch on any other stream would not).  A buffer that could not be allocated is left empty.
+enum : unsigned { kSyncDevice = 1, kSyncScan = 2, kZeroFill = 4 };
+struct Want {
+    DevMem& buf;
+    size_t bytes;
+};
+static int reserve(pgn_ctx* c, std::initializer_list<Want> group, unsigned flags = 0, hipStream_t also = nullptr)
 {
-    if (slots > c->encSlots) {
-        wait_last_host(c);
-        (void)hipFree(c->encScratch);
-        (void)hipFree(c->epochs);
-        c->encScratch = nullptr;
-        c->epochs = nullptr;
-        const size_t sb = enc_slot_bytes();
-        HIPCHK(hipMalloc(&c->encScratch, sb * slots));
-        HIPCHK(hipMalloc(&c->epochs, 4 * slots));
-        // tag 0 never matches: a zeroed table is an empty table for every epoch >= 1.  The context
-        // stream is non-blocking, so zero on it and wait before any launch (on any stream) uses it.
-        HIPCHK(hipMemsetAsync(c->epochs, 0, 4 * slots, c->stream));
-        HIPCHK(hipMemsetAsync(c->encScratch, 0, sb * slots, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->encSlots = slots;
+    bool fits = true;
+    for (const Want& w : group) fits = fits && w.bytes <= w.buf.cap;
+    if (fits) return PGN_OK;
+    wait_last_host(c);
+    if (flags & kSyncDevice) (void)hipDeviceSynchronize();
+    if (flags & kSyncScan) (void)hipStreamSynchronize(c->scanStream);
+    if (also) (void)hipStreamSynchronize(also);
+    for (const Want& w : group) {
+        (void)hipFree(w.buf.p);
+        w.buf.p = nullptr;
+        w.buf.cap = 0;
     }
-    if (G > c->encG) {  // G = chunk capacity over all buffers
-        wait_last_host(c);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(c->encChunks);
-        c->encChunks = nullptr;
-        HIPCHK(hipMalloc(&c->encChunks, G * (kChunkStreamBytes + kChunkFrameBytes + 2 * 4 * kStreams)));
-        c->encG = G;
+    for (const Want& w : group) HIPCHK(dev_alloc(w.buf, w.bytes));
+    if (flags & kZeroFill) {
+        for (const Want& w : group) HIPCHK(hipMemsetAsync(w.buf.p, 0, w.bytes, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
     return PGN_OK;
 }
 
+// One call's launch sequence on a context: it takes the context's lock (unless the caller holds it: the
+// per-chunk host calls, and a decode inside a read call), makes the device current, picks the stream and
+// orders it behind the previous sequence (evLast, whatever stream that ran on).  However the scope is
+// left, by an error too, it records evLast behind what the call queued, so the next call on another
+// stream never overtakes kernels that still use the context's scratch.
+struct CallScope {
+    enum Lock { kLock, kLocked };
+    pgn_ctx* const c;
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    int rc = PGN_OK;  // not PGN_OK: the scope did not open, and the call returns this
+    CallScope(pgn_ctx* ctx, void* stream, Lock l = kLock) : c(ctx)
+    {
+        if (l == kLock) lock = std::unique_lock<std::mutex>(c->mu);
+        rc = open(stream);
+    }
+    ~CallScope()
+    {
+        if (rc == PGN_OK && hipEventRecord(c->evLast, s) == hipSuccess) c->haveLast = true;
+    }
+    CallScope(const CallScope&) = delete;
+    CallScope& operator=(const CallScope&) = delete;
+
+private:
+    int open(void* stream)
+    {
+        HIPCHK(hipSetDevice(c->device));
+        s = stream ? (hipStream_t)stream : c->stream;
+        if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+        return PGN_OK;
+    }
+};
+
+static int ensure_enc(pgn_ctx* c, size_t slots, size_t G)
+{
+    // tag 0 never matches: a zeroed table is an empty table for every epoch >= 1
+    int rc = reserve(c, {{c->encScratch, enc_slot_bytes() * slots}, {c->epochs, 4 * slots}}, kZeroFill);
+    if (rc) return rc;
+    // G = chunk capacity over all buffers
+    return reserve(c, {{c->encChunks, G * (kChunkStreamBytes + kChunkFrameBytes + 2 * 4 * kStreams)}}, kSyncDevice);
+}
+
 static int ensure_dec(pgn_ctx* c, size_t slots, size_t bytes)
 {
-    if (slots > c->decSlots) {
-        wait_last_host(c);
-        (void)hipFree(c->decScratch);
-        c->decScratch = nullptr;
-        HIPCHK(hipMalloc(&c->decScratch, dec_slot_bytes() * slots));
-        c->decSlots = slots;
-    }
-    if (bytes > c->decBytes) {  // the per-chunk buffers of all passes in flight
-        wait_last_host(c);
-        (void)hipDeviceSynchronize();
-        (void)hipFree(c->decChunks);
-        c->decChunks = nullptr;
-        HIPCHK(hipMalloc(&c->decChunks, bytes));
-        c->decBytes = bytes;
-    }
-    return PGN_OK;
+    int rc = reserve(c, {{c->decScratch, dec_slot_bytes() * slots}});
+    if (rc) return rc;
+    return reserve(c, {{c->decChunks, bytes}}, kSyncDevice);  // the per-chunk buffers of all passes in flight
 }
 
 // The look-back words of the small-batch range split / merge and this call's tag.  Launch sequences
@@ -2425,7 +2445,7 @@ static int take_lookback(pgn_ctx* c, hipStream_t s, uint64_t*& words, uint64_t& 
 {
     const size_t bytes = sizeof(uint64_t) * 3 * 32 * 64;  // 3 words x 32 ranges x 64 chunks
     if (!c->lookback) {
-        HIPCHK(hipMalloc(&c->lookback, bytes));
+        HIPCHK(dev_alloc(c->lookback, bytes));
         HIPCHK(hipMemsetAsync(c->lookback, 0, bytes, s));
     }
     if (++c->lbEpoch > 0xFFFFu) {
@@ -2444,19 +2464,11 @@ static int take_lookback(pgn_ctx* c, hipStream_t s, uint64_t*& words, uint64_t& 
 static int ensure_queues(pgn_ctx* c, size_t n, hipStream_t s)
 {
     constexpr size_t kRing = 1 << 14;
-    if (!c->queues || n > c->nQueues) {
-        wait_last_host(c);
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(c->queues);
-        c->queues = nullptr;
-        const size_t m = n < kRing ? kRing : n;
-        HIPCHK(hipMalloc(&c->queues, 4 * m));
-        HIPCHK(hipMemsetAsync(c->queues, 0, 4 * m, s));
-        c->nQueues = m;
-        c->qNext = 0;
-    }
-    if (c->qNext + n > c->nQueues) {
-        HIPCHK(hipMemsetAsync(c->queues, 0, 4 * c->nQueues, s));
+    const size_t had = c->queues.cap;
+    const int rc = reserve(c, {{c->queues, 4 * (n < kRing ? kRing : n)}}, 0, s);
+    if (rc) return rc;
+    if (c->queues.cap != had || c->qNext + n > c->queues.cap / 4) {  // a new ring, or the ring wraps
+        HIPCHK(hipMemsetAsync(c->queues, 0, c->queues.cap, s));
         c->qNext = 0;
     }
     c->qCur = c->queues + c->qNext;
@@ -2473,22 +2485,73 @@ struct DecOut {
     DecOut(int16_t* samples) : p(samples), type(PGN_OUT_INT16), calOffset(nullptr), calScale(nullptr) {}
     DecOut(void* out, int t, const float* off, const float* scale) : p(out), type(t), calOffset(off), calScale(scale) {}
 };
-static void set_out(DecArgs& a, const DecOut& o)
+
+// The caller's device arrays of an encode / a decode call, one entry per chunk, as the C entry points
+// receive them.  Everything below the entry points passes them on as one.
+struct EncIO {
+    const int16_t* samples;
+    const uint64_t* sampleOffsets;
+    const uint32_t* sampleCounts;
+    uint8_t* out;
+    const uint64_t* outOffsets;
+    const uint64_t* outCaps;
+    uint64_t* outSizes;
+    int32_t* status;
+    uint64_t* stats;
+};
+struct DecIO {
+    const uint8_t* in;
+    const uint64_t* inOffsets;
+    const uint64_t* inSizes;
+    DecOut out;
+    const uint64_t* sampleOffsets;
+    const uint32_t* sampleCounts;
+    int32_t* status;
+};
+
+// The launch arguments every encode / decode path starts from: what comes from the caller and what is the
+// same for the whole context (taken after the path's ensure_*, which may move the context's buffers).  A
+// path then sets only what it differs in: slot scratch, queue, capN, the list, the passes' geometry.
+static EncArgs enc_args(const pgn_ctx* c, const EncIO& io, size_t nchunks)
 {
-    a.samples = (int16_t*)o.p;
-    a.outBytes = (uint8_t*)o.p;
-    a.outType = o.type;
-    a.calOffset = o.calOffset;
-    a.calScale = o.calScale;
+    EncArgs a{};
+    a.nchunks = nchunks;
+    a.samples = io.samples;
+    a.sampleOffsets = io.sampleOffsets;
+    a.sampleCounts = io.sampleCounts;
+    a.out = io.out;
+    a.outOffsets = io.outOffsets;
+    a.outCaps = io.outCaps;
+    a.outSizes = io.outSizes;
+    a.status = io.status;
+    a.stats = io.stats;
+    a.epochs = c->epochs;
+    a.prof = c->prof;
+    return a;
+}
+static DecArgs dec_args(const pgn_ctx* c, const DecIO& io, size_t nchunks)
+{
+    DecArgs a{};
+    a.nchunks = nchunks;
+    a.in = io.in;
+    a.inOffsets = io.inOffsets;
+    a.inSizes = io.inSizes;
+    a.samples = (int16_t*)io.out.p;
+    a.outBytes = (uint8_t*)io.out.p;
+    a.outType = io.out.type;
+    a.calOffset = io.out.calOffset;
+    a.calScale = io.out.calScale;
+    a.sampleOffsets = io.sampleOffsets;
+    a.sampleCounts = io.sampleCounts;
+    a.status = io.status;
+    a.prof = c->prof ? c->prof + kPhases : nullptr;
+    return a;
 }
 
 static int launch_enc_chunks(int codec, const EncArgs& a, size_t slots, hipStream_t s);
 static int launch_dec_chunks(int codec, const DecArgs& a, size_t slots, hipStream_t s);
 
-static int launch_encode_fused(pgn_ctx* c, int codec, size_t nchunks, const int16_t* d_samples,
-                               const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts, uint8_t* d_out,
-                               const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_sizes,
-                               int32_t* d_status, uint64_t* d_stats, hipStream_t s)
+static int launch_encode_fused(pgn_ctx* c, int codec, size_t nchunks, const EncIO& io, hipStream_t s)
 {
     const size_t slots = nchunks < c->encFusedSlotsMax ? nchunks : c->encFusedSlotsMax;
     int rc = ensure_enc(c, slots, 0);
@@ -2496,24 +2559,11 @@ static int launch_encode_fused(pgn_ctx* c, int codec, size_t nchunks, const int1
     HIPCHK(hipEventRecord(c->ev[0], s));
     rc = ensure_queues(c, 1, s);
     if (rc) return rc;
-    EncArgs a{};
-    a.nchunks = nchunks;
-    a.samples = d_samples;
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.out = d_out;
-    a.outOffsets = d_out_offsets;
-    a.outCaps = d_out_caps;
-    a.outSizes = d_out_sizes;
-    a.status = d_status;
-    a.stats = d_stats;
+    EncArgs a = enc_args(c, io, nchunks);
     a.slotScratch = c->encScratch;
     a.slotBytes = enc_slot_bytes();
-    a.epochs = c->epochs;
-    a.prof = c->prof;
     a.queue = c->qCur;
     a.capN = kPassSamples;
-    a.list = nullptr;
     return launch_enc_chunks(codec, a, slots, s);
 }
 
@@ -2533,9 +2583,7 @@ static int launch_enc_chunks(int codec, const EncArgs& a, size_t slots, hipStrea
     return PGN_OK;
 }
 
-static int launch_decode_fused(pgn_ctx* c, int codec, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                               const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
-                               const uint32_t* d_sample_counts, int32_t* d_status, hipStream_t s)
+static int launch_decode_fused(pgn_ctx* c, int codec, size_t nchunks, const DecIO& io, hipStream_t s)
 {
     const size_t slots = nchunks < c->decFusedSlotsMax ? nchunks : c->decFusedSlotsMax;
     int rc = ensure_dec(c, slots, 0);
@@ -2543,21 +2591,11 @@ static int launch_decode_fused(pgn_ctx* c, int codec, size_t nchunks, const uint
     HIPCHK(hipEventRecord(c->ev[2], s));
     rc = ensure_queues(c, 1, s);
     if (rc) return rc;
-    DecArgs a{};
-    a.nchunks = nchunks;
-    a.in = d_in;
-    a.inOffsets = d_in_offsets;
-    a.inSizes = d_in_sizes;
-    set_out(a, d_samples);
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.status = d_status;
+    DecArgs a = dec_args(c, io, nchunks);
     a.slotScratch = c->decScratch;
     a.slotBytes = dec_slot_bytes();
-    a.prof = c->prof ? c->prof + kPhases : nullptr;
     a.queue = c->qCur;
     a.capN = kPassSamples;
-    a.list = nullptr;
     c->lastUnits = nullptr;
     return launch_dec_chunks(codec, a, slots, s);
 }
@@ -2578,17 +2616,11 @@ static int launch_dec_chunks(int codec, const DecArgs& a, size_t slots, hipStrea
     return PGN_OK;
 }
 
-static int launch_encode_impl(pgn_ctx* c, int codec, size_t nchunks, const int16_t* d_samples, const uint64_t* d_sample_offsets,
-                         const uint32_t* d_sample_counts, uint8_t* d_out, const uint64_t* d_out_offsets,
-                         const uint64_t* d_out_caps, uint64_t* d_out_sizes, int32_t* d_status, uint64_t* d_stats,
-                         void* stream)
+static int launch_encode_impl(pgn_ctx* c, int codec, size_t nchunks, const EncIO& io, hipStream_t s)
 {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     const bool staged = c->encStaged || (!c->encForced && nchunks <= c->encStagedBelow);
     if (!staged || (codec != kCodecC5 && codec != kCodecVbz))  // the other variants are fused only
-        return launch_encode_fused(c, codec, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets,
-                                   d_out_caps, d_out_sizes, d_status, d_stats, s);
+        return launch_encode_fused(c, codec, nchunks, io, s);
     const size_t G = nchunks < c->subBatch ? nchunks : c->subBatch;
     const size_t passes = (nchunks + G - 1) / G;
     const uint32_t nu = codec == kCodecVbz ? 1u : (uint32_t)kStreams;
@@ -2607,27 +2639,12 @@ static int launch_encode_impl(pgn_ctx* c, int codec, size_t nchunks, const int16
         HIPCHK(hipStreamWaitEvent(c->side, c->evFork, 0));
     }
     const size_t bufBytes = G * (kChunkStreamBytes + kChunkFrameBytes + 2 * 4 * kStreams);
-    EncArgs a{};
-    a.nchunks = nchunks;
-    a.samples = d_samples;
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.out = d_out;
-    a.outOffsets = d_out_offsets;
-    a.outCaps = d_out_caps;
-    a.outSizes = d_out_sizes;
-    a.status = d_status;
-    a.stats = d_stats;
+    EncArgs a = enc_args(c, io, nchunks);
     a.slotScratch = c->encScratch;
     a.slotBytes = enc_slot_bytes();
-    a.epochs = c->epochs;
-    a.prof = c->prof;
     a.G = G;
     a.nu = nu;
     a.capN = kPassSamples;
-    a.list = nullptr;
-    a.lookback = nullptr;
-    a.epoch = 0;
     if (passes == 1 && G <= kSplitWgMaxChunks && codec != kCodecVbz) {  // the look-back range split (one epoch per pass)
         rc = take_lookback(c, s, a.lookback, a.epoch);
         if (rc) return rc;
@@ -2685,15 +2702,9 @@ static void launch_merge(int codec, const DecArgs& a, size_t G, hipStream_t ms)
 
 // capCall: every chunk of the call has at most this many samples (a multiple of 4096, at most
 // kPassSamples); the per-chunk intermediates are spaced for it.
-static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                         const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
-                         const uint32_t* d_sample_counts, int32_t* d_status, void* stream, uint32_t capCall)
+static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const DecIO& io, hipStream_t s, uint32_t capCall)
 {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!c->decStaged || (codec != kCodecC5 && codec != kCodecVbz))
-        return launch_decode_fused(c, codec, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                                   d_sample_counts, d_status, s);
+    if (!c->decStaged || (codec != kCodecC5 && codec != kCodecVbz)) return launch_decode_fused(c, codec, nchunks, io, s);
     // large C5 batches: deferred Huffman sections (dec_huf_kernel), passes of up to deferG chunks
     // balanced over the batch; otherwise passes of subBatch chunks
     bool defer = codec == kCodecC5 && nchunks >= c->deferMin;
@@ -2708,22 +2719,16 @@ static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8
         size_t gmax = kDecBufferBudget / (c->decBufs * (stride + kStreams * (sizeof(DecUnit) + kJobBytes)));
         gmax = gmax < c->subBatch ? c->subBatch : gmax;
         gmax = gmax < c->deferG ? gmax : c->deferG;
-        // an optional short first pass (PGN_DEFER_HEAD: the sections start sooner), the passes of up to
-        // gmax chunks balanced over the rest, and an optional in-place tail pass (PGN_DEFER_TAIL_PLAIN)
-        size_t head = c->deferHead, tail = c->deferTailPlain;
-        if (!(head > 0 && head <= gmax && nchunks >= 4 * head)) head = 0;
-        if (!(tail > 0 && tail <= gmax && nchunks - head >= 2 * tail)) tail = 0;
-        if (head) {
-            pBase.push_back(0);
-            pCnt.push_back(head);
-            pPlain.push_back(0);
-        }
-        const size_t mid = nchunks - head - tail;
+        // the passes of up to gmax chunks balanced over the batch, less an optional in-place tail pass
+        // (PGN_DEFER_TAIL_PLAIN)
+        size_t tail = c->deferTailPlain;
+        if (!(tail > 0 && tail <= gmax && nchunks >= 2 * tail)) tail = 0;
+        const size_t mid = nchunks - tail;
         const size_t np = (mid + gmax - 1) / gmax;
         const size_t Gd = (mid + np - 1) / np;
-        for (size_t b = head; b < head + mid; b += Gd) {
+        for (size_t b = 0; b < mid; b += Gd) {
             pBase.push_back(b);
-            pCnt.push_back(head + mid - b < Gd ? head + mid - b : Gd);
+            pCnt.push_back(mid - b < Gd ? mid - b : Gd);
             pPlain.push_back(0);
         }
         if (tail) {
@@ -2776,25 +2781,13 @@ static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8
         HIPCHK(hipEventRecord(c->evFork, s));
         HIPCHK(hipStreamWaitEvent(c->side, c->evFork, 0));
     }
-    DecArgs a{};
-    a.nchunks = nchunks;
-    a.in = d_in;
-    a.inOffsets = d_in_offsets;
-    a.inSizes = d_in_sizes;
-    set_out(a, d_samples);
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.status = d_status;
+    DecArgs a = dec_args(c, io, nchunks);
     a.slotScratch = c->decScratch;
     a.slotBytes = dec_slot_bytes();
-    a.prof = c->prof ? c->prof + kPhases : nullptr;
     a.G = G;
     a.nu = nu;
     a.capN = capCall;
     a.interStride = stride;
-    a.list = nullptr;
-    a.lookback = nullptr;
-    a.epoch = 0;
     if (passes == 1 && G <= kMergeWgMaxChunks && codec != kCodecVbz) {  // the look-back range merge (one epoch per pass)
         const int lrc = take_lookback(c, s, a.lookback, a.epoch);
         if (lrc) return lrc;
@@ -2823,11 +2816,7 @@ static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8
             hipLaunchKernelGGL(dec_zstd_coop_kernel, dim3((unsigned)(nu * G)), dim3(64 * kCoopWaves), 0, s, a);
         else hipLaunchKernelGGL(dec_zstd_kernel, dim3((unsigned)slots), dim3(64), 0, s, a);
         // the stream of this pass's sections (deferred) or merge (otherwise)
-        // (the last pass's on the caller's stream, right behind its frame decode: on side stream p % 3
-        // they would queue behind pass p - 3's merge, which ends ~1 ms after the frame decode,
-        // profiles/r06_decode_timeline_a.txt)
-        const bool lastOnCaller = defer && c->lastOnCaller && p + 1 == passes;
-        const hipStream_t hs = multi ? (defer ? (lastOnCaller ? s : hufS[p % hufStreams]) : c->side) : sideS;
+        const hipStream_t hs = multi ? (defer ? hufS[p % hufStreams] : c->side) : sideS;
         if (multi && hs != s) {
             HIPCHK(hipEventRecord(c->evDStage[b], s));
             HIPCHK(hipStreamWaitEvent(hs, c->evDStage[b], 0));
@@ -2869,27 +2858,20 @@ static int launch_decode_impl(pgn_ctx* c, int codec, size_t nchunks, const uint8
 // largest of them.  Chunks above PGN_MAX_CHUNK_SAMPLES stay UNSUPPORTED.
 static bool need_scan(uint32_t maxHint) { return maxHint == 0 || maxHint > kPassSamples; }
 
-// decode calls also list the chunks of the claims pass (claim_scan_kernel), given their blobs
-struct ScanBlobs {
-    const uint8_t* in;
-    const uint64_t* offsets;
-    const uint64_t* sizes;
-    int nf;
-};
-static int start_scan(pgn_ctx* c, size_t nchunks, const uint32_t* d_counts, hipStream_t s,
-                      const ScanBlobs* blobs = nullptr)
+// the large pass's and the claims pass's lists, for n chunks (at least 4,096 entries each)
+static int ensure_lists(pgn_ctx* c, size_t n)
 {
-    if (nchunks > c->largeListCap) {
-        wait_last_host(c);
-        (void)hipStreamSynchronize(c->scanStream);
-        (void)hipFree(c->largeList);
-        (void)hipFree(c->claimList);
-        c->largeList = c->claimList = nullptr;
-        const size_t m = nchunks < 4096 ? 4096 : nchunks;
-        HIPCHK(hipMalloc(&c->largeList, 4 * m));
-        HIPCHK(hipMalloc(&c->claimList, 4 * m));
-        c->largeListCap = m;
-    }
+    const size_t bytes = 4 * (n < 4096 ? 4096 : n);
+    return reserve(c, {{c->largeList, bytes}, {c->claimList, bytes}}, kSyncScan);
+}
+
+// dec: a decode call's arrays, whose scan also lists the chunks of the claims pass (claim_scan_kernel;
+// nf: the codec's frames per chunk)
+static int start_scan(pgn_ctx* c, size_t nchunks, const uint32_t* d_counts, hipStream_t s, const DecIO* dec = nullptr,
+                      int nf = 0)
+{
+    const int rc = ensure_lists(c, nchunks);
+    if (rc) return rc;
     HIPCHK(hipEventRecord(c->evScanFork, s));
     HIPCHK(hipStreamWaitEvent(c->scanStream, c->evScanFork, 0));
     HIPCHK(hipMemsetAsync(c->largeHdr, 0, 8 * sizeof(uint32_t), c->scanStream));
@@ -2897,9 +2879,9 @@ static int start_scan(pgn_ctx* c, size_t nchunks, const uint32_t* d_counts, hipS
     grid = grid > 1024 ? 1024 : grid;
     hipLaunchKernelGGL(large_scan_kernel, dim3(grid), dim3(256), 0, c->scanStream, d_counts, nchunks, c->largeList,
                        c->largeHdr);
-    if (blobs)
-        hipLaunchKernelGGL(claim_scan_kernel, dim3(grid), dim3(256), 0, c->scanStream, blobs->in, blobs->offsets,
-                           blobs->sizes, d_counts, nchunks, blobs->nf, c->claimList, c->largeHdr);
+    if (dec)
+        hipLaunchKernelGGL(claim_scan_kernel, dim3(grid), dim3(256), 0, c->scanStream, dec->in, dec->inOffsets,
+                           dec->inSizes, d_counts, nchunks, nf, c->claimList, c->largeHdr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(c->largeHdrHost, c->largeHdr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->scanStream));
     HIPCHK(hipEventRecord(c->evScan, c->scanStream));
@@ -2916,36 +2898,10 @@ static uint32_t large_cap(uint32_t maxN)
 }
 static int ensure_large_enc(pgn_ctx* c, size_t bytes, size_t epochSlots)
 {
-    if (bytes > c->largeScratchBytes || epochSlots > c->largeEpochSlots) {
-        wait_last_host(c);
-        (void)hipFree(c->largeScratch);
-        (void)hipFree(c->largeEpochs);
-        c->largeScratch = nullptr;
-        c->largeEpochs = nullptr;
-        c->largeScratchBytes = c->largeEpochSlots = 0;
-        HIPCHK(hipMalloc(&c->largeScratch, bytes));
-        HIPCHK(hipMalloc(&c->largeEpochs, 4 * epochSlots));
-        // fresh tables: tag 0 never matches (as in ensure_enc)
-        HIPCHK(hipMemsetAsync(c->largeEpochs, 0, 4 * epochSlots, c->stream));
-        HIPCHK(hipMemsetAsync(c->largeScratch, 0, bytes, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->largeScratchBytes = bytes;
-        c->largeEpochSlots = epochSlots;
-    }
-    return PGN_OK;
+    // fresh tables: tag 0 never matches (as in ensure_enc)
+    return reserve(c, {{c->largeScratch, bytes}, {c->largeEpochs, 4 * epochSlots}}, kZeroFill);
 }
-static int ensure_large_dec(pgn_ctx* c, size_t bytes)
-{
-    if (bytes > c->largeDecScratchBytes) {
-        wait_last_host(c);
-        (void)hipFree(c->largeDecScratch);
-        c->largeDecScratch = nullptr;
-        c->largeDecScratchBytes = 0;
-        HIPCHK(hipMalloc(&c->largeDecScratch, bytes));
-        c->largeDecScratchBytes = bytes;
-    }
-    return PGN_OK;
-}
+static int ensure_large_dec(pgn_ctx* c, size_t bytes) { return reserve(c, {{c->largeDecScratch, bytes}}); }
 static size_t large_slots(pgn_ctx* c, uint32_t count, size_t slotBytes, size_t fusedMax)
 {
     size_t slots = count < fusedMax ? count : fusedMax;
@@ -2968,11 +2924,7 @@ static uint32_t call_cap(uint32_t maxN)
     return r < 4096u ? 4096u : (r > kPassSamples ? kPassSamples : r);
 }
 
-static int launch_large_encode(pgn_ctx* c, int codec, uint32_t count, uint32_t maxN, size_t nchunks,
-                               const int16_t* d_samples, const uint64_t* d_sample_offsets,
-                               const uint32_t* d_sample_counts, uint8_t* d_out, const uint64_t* d_out_offsets,
-                               const uint64_t* d_out_caps, uint64_t* d_out_sizes, int32_t* d_status, uint64_t* d_stats,
-                               hipStream_t s)
+static int launch_large_encode(pgn_ctx* c, int codec, uint32_t count, uint32_t maxN, const EncIO& io, hipStream_t s)
 {
     const uint32_t capN = large_cap(maxN);
     const size_t sb = enc_slot_bytes(capN);
@@ -2980,32 +2932,17 @@ static int launch_large_encode(pgn_ctx* c, int codec, uint32_t count, uint32_t m
     int rc = ensure_large_enc(c, sb * slots, slots);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->largeHdr + 2, 0, sizeof(uint32_t), s));
-    EncArgs a{};
-    a.nchunks = count;
-    a.samples = d_samples;
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.out = d_out;
-    a.outOffsets = d_out_offsets;
-    a.outCaps = d_out_caps;
-    a.outSizes = d_out_sizes;
-    a.status = d_status;
-    a.stats = d_stats;
+    EncArgs a = enc_args(c, io, count);
     a.slotScratch = c->largeScratch;
     a.slotBytes = sb;
-    a.epochs = c->largeEpochs;
-    a.prof = c->prof;
+    a.epochs = c->largeEpochs;  // the large pass's own tables
     a.queue = c->largeHdr + 2;
     a.capN = capN;
     a.list = c->largeList;
-    (void)nchunks;
     return launch_enc_chunks(codec, a, slots, s);
 }
 
-static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t maxN, const uint8_t* d_in,
-                               const uint64_t* d_in_offsets, const uint64_t* d_in_sizes, const DecOut& d_samples,
-                               const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts, int32_t* d_status,
-                               hipStream_t s)
+static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t maxN, const DecIO& io, hipStream_t s)
 {
     const uint32_t capN = large_cap(maxN);
     const size_t sb = dec_slot_bytes(capN);
@@ -3013,18 +2950,9 @@ static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t m
     int rc = ensure_large_dec(c, sb * slots);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->largeHdr + 2, 0, sizeof(uint32_t), s));
-    DecArgs a{};
-    a.nchunks = count;
-    a.in = d_in;
-    a.inOffsets = d_in_offsets;
-    a.inSizes = d_in_sizes;
-    set_out(a, d_samples);
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.status = d_status;
+    DecArgs a = dec_args(c, io, count);
     a.slotScratch = c->largeDecScratch;
     a.slotBytes = sb;
-    a.prof = c->prof ? c->prof + kPhases : nullptr;
     a.queue = c->largeHdr + 2;
     a.capN = capN;
     a.list = c->largeList;
@@ -3037,9 +2965,7 @@ static int launch_large_decode(pgn_ctx* c, int codec, uint32_t count, uint32_t m
 // their statuses and samples replace the batched pass's.  The fused kernel, slot scratch of the
 // large pass (ordered after it on the stream).
 static int launch_claims_decode(pgn_ctx* c, int codec, uint32_t count, uint64_t maxSum, const uint32_t* list,
-                                const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_sizes,
-                                const DecOut& d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts,
-                                int32_t* d_status, hipStream_t s)
+                                const DecIO& io, hipStream_t s)
 {
     const uint64_t cap = (maxSum < kClaimPassMax ? maxSum : kClaimPassMax) + kVbzPadding;
     const size_t sb = dec_layout().bytes + align_up(cap + 64, 256);
@@ -3047,18 +2973,9 @@ static int launch_claims_decode(pgn_ctx* c, int codec, uint32_t count, uint64_t 
     int rc = ensure_large_dec(c, sb * slots);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(c->largeHdr + 2, 0, sizeof(uint32_t), s));
-    DecArgs a{};
-    a.nchunks = count;
-    a.in = d_in;
-    a.inOffsets = d_in_offsets;
-    a.inSizes = d_in_sizes;
-    set_out(a, d_samples);
-    a.sampleOffsets = d_sample_offsets;
-    a.sampleCounts = d_sample_counts;
-    a.status = d_status;
+    DecArgs a = dec_args(c, io, count);
     a.slotScratch = c->largeDecScratch;
     a.slotBytes = sb;
-    a.prof = c->prof ? c->prof + kPhases : nullptr;
     a.queue = c->largeHdr + 2;
     a.capN = PGN_MAX_CHUNK_SAMPLES;
     a.list = list;
@@ -3070,10 +2987,7 @@ static int launch_claims_decode(pgn_ctx* c, int codec, uint32_t count, uint64_t 
 // among [0, n) whose status came back PGN_ERR_UNSUPPORTED are listed on the host from their own bytes
 // (the device arrays describe the same chunks); then the pass runs and the call waits for it.
 static int claims_from_host(pgn_ctx* c, int codec, size_t n, const int32_t* status, const uint32_t* counts,
-                            const uint8_t* const* blobs, const uint64_t* blobLens, const uint8_t* d_in,
-                            const uint64_t* d_in_offsets, const uint64_t* d_in_sizes, const DecOut& d_samples,
-                            const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts, int32_t* d_status,
-                            hipStream_t s)
+                            const uint8_t* const* blobs, const uint64_t* blobLens, const DecIO& io, hipStream_t s)
 {
     uint32_t idx[kPcMaxReqs];
     uint32_t k = 0;
@@ -3087,114 +3001,80 @@ static int claims_from_host(pgn_ctx* c, int codec, size_t n, const int32_t* stat
         maxSum = sum > maxSum ? sum : maxSum;
     }
     if (k == 0) return PGN_OK;
-    if (!c->claimList || c->largeListCap < kPcMaxReqs) {
-        const size_t m = c->largeListCap > 4096 ? c->largeListCap : 4096;
-        (void)hipFree(c->claimList);
-        (void)hipFree(c->largeList);
-        c->claimList = c->largeList = nullptr;
-        HIPCHK(hipMalloc(&c->largeList, 4 * m));
-        HIPCHK(hipMalloc(&c->claimList, 4 * m));
-        c->largeListCap = m;
-    }
+    int rc = ensure_lists(c, kPcMaxReqs);  // allocates them when no scan has yet
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->claimList, idx, 4 * k, hipMemcpyHostToDevice, s));
-    const int rc = launch_claims_decode(c, codec, k, maxSum, c->claimList, d_in, d_in_offsets, d_in_sizes, d_samples,
-                                        d_sample_offsets, d_sample_counts, d_status, s);
+    rc = launch_claims_decode(c, codec, k, maxSum, c->claimList, io, s);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));
     return PGN_OK;
 }
 
-// Every launch sequence on a context: ordered after the previous one (evLast, whatever its stream),
-// and recorded as the new last one.  ev[0..1] / ev[2..3] bracket the call's kernels.
-static int launch_encode(pgn_ctx* c, int codec, size_t nchunks, const int16_t* d_samples, const uint64_t* d_sample_offsets,
-                         const uint32_t* d_sample_counts, uint8_t* d_out, const uint64_t* d_out_offsets,
-                         const uint64_t* d_out_caps, uint64_t* d_out_sizes, int32_t* d_status, uint64_t* d_stats,
-                         void* stream, uint32_t maxHint)
+// The encode / decode launch sequence of one call (a CallScope; `lock`: whether the caller already holds
+// the context's lock).  ev[0..1] / ev[2..3] bracket the call's kernels.
+static int launch_encode(pgn_ctx* c, int codec, size_t nchunks, const EncIO& io, void* stream, uint32_t maxHint,
+                         CallScope::Lock lock)
 {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream, lock);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     const bool scan = need_scan(maxHint);
-    int rc = scan ? start_scan(c, nchunks, d_sample_counts, s) : PGN_OK;
-    if (rc == PGN_OK)
-        rc = launch_encode_impl(c, codec, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets,
-                                d_out_caps, d_out_sizes, d_status, d_stats, s);
+    int rc = scan ? start_scan(c, nchunks, io.sampleCounts, s) : PGN_OK;
+    if (rc == PGN_OK) rc = launch_encode_impl(c, codec, nchunks, io, s);
     uint32_t count = 0, maxN = 0;
     if (rc == PGN_OK && scan) rc = finish_scan(c, count, maxN);
-    if (rc == PGN_OK && count)
-        rc = launch_large_encode(c, codec, count, maxN, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out,
-                                 d_out_offsets, d_out_caps, d_out_sizes, d_status, d_stats, s);
+    if (rc == PGN_OK && count) rc = launch_large_encode(c, codec, count, maxN, io, s);
     if (rc == PGN_OK) {
         HIPCHK(hipEventRecord(c->ev[1], s));
         c->encTimed = true;
     }
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return rc;
 }
 
-static int launch_decode(pgn_ctx* c, int codec, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                         const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
-                         const uint32_t* d_sample_counts, int32_t* d_status, void* stream, uint32_t maxHint)
+static int launch_decode(pgn_ctx* c, int codec, size_t nchunks, const DecIO& io, void* stream, uint32_t maxHint,
+                         CallScope::Lock lock)
 {
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream, lock);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     const bool scan = need_scan(maxHint);
     // The intermediates are spaced for the call's largest chunk when the caller bounds it, else for
     // kPassSamples (the scan then runs beside the batched pass, and the launch stays asynchronous).
     uint32_t capCall = (!scan && maxHint) ? call_cap(maxHint) : kPassSamples;
     uint32_t count = 0, maxN = 0;
-    const ScanBlobs blobs{d_in, d_in_offsets, d_in_sizes, codec_frames(codec)};
-    int rc = scan ? start_scan(c, nchunks, d_sample_counts, s, &blobs) : PGN_OK;
+    int rc = scan ? start_scan(c, nchunks, io.sampleCounts, s, &io, codec_frames(codec)) : PGN_OK;
     // small calls (the per-chunk ones) keep the full capacity: a frame is then decoded up to its own
     // content size, as the reference does, and the chunk ends with its statuses (e.g. "Remaining
     // data" for samples fewer than the frames hold) rather than PGN_ERR_UNSUPPORTED
     if (nchunks <= kCoopMaxChunks) capCall = kPassSamples;
-    if (rc == PGN_OK)
-        rc = launch_decode_impl(c, codec, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                                d_sample_counts, d_status, s, capCall);
+    if (rc == PGN_OK) rc = launch_decode_impl(c, codec, nchunks, io, s, capCall);
     if (rc == PGN_OK && scan) rc = finish_scan(c, count, maxN);
-    if (rc == PGN_OK && count)
-        rc = launch_large_decode(c, codec, count, maxN, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                                 d_sample_counts, d_status, s);
+    if (rc == PGN_OK && count) rc = launch_large_decode(c, codec, count, maxN, io, s);
     // the chunks whose frames claim more than the passes' intermediates hold (listed by the scan)
     if (rc == PGN_OK && scan && c->largeHdrHost[4])
-        rc = launch_claims_decode(c, codec, c->largeHdrHost[4], (uint64_t)c->largeHdrHost[5] << 10, c->claimList, d_in,
-                                  d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts, d_status, s);
+        rc = launch_claims_decode(c, codec, c->largeHdrHost[4], (uint64_t)c->largeHdrHost[5] << 10, c->claimList, io, s);
     if (rc == PGN_OK) {
         HIPCHK(hipEventRecord(c->ev[3], s));
         c->decTimed = true;
     }
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return rc;
 }
 
-static int compress_batch(int codec, pgn_ctx* c, size_t nchunks, const int16_t* d_samples,
-                          const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts, uint8_t* d_out,
-                          const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_sizes,
-                          int32_t* d_status, uint64_t* d_stats, void* stream, uint32_t maxHint = 0)
+static int compress_batch(int codec, pgn_ctx* c, size_t nchunks, const EncIO& io, void* stream, uint32_t maxHint = 0)
 {
-    if (!c || !d_samples || !d_sample_offsets || !d_sample_counts || !d_out || !d_out_offsets || !d_out_caps ||
-        !d_out_sizes || !d_status)
+    if (!c || !io.samples || !io.sampleOffsets || !io.sampleCounts || !io.out || !io.outOffsets || !io.outCaps ||
+        !io.outSizes || !io.status)
         return PGN_ERR_INVALID_ARG;
     if (nchunks == 0) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    return launch_encode(c, codec, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps,
-                         d_out_sizes, d_status, d_stats, stream, maxHint);
+    return launch_encode(c, codec, nchunks, io, stream, maxHint, CallScope::kLock);
 }
 
-static int decompress_batch(int codec, pgn_ctx* c, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
-                            const uint64_t* d_in_sizes, const DecOut& d_samples, const uint64_t* d_sample_offsets,
-                            const uint32_t* d_sample_counts, int32_t* d_status, void* stream, uint32_t maxHint = 0)
+static int decompress_batch(int codec, pgn_ctx* c, size_t nchunks, const DecIO& io, void* stream, uint32_t maxHint = 0)
 {
-    if (!c || !d_in || !d_in_offsets || !d_in_sizes || !d_samples.p || !d_sample_offsets || !d_sample_counts || !d_status)
+    if (!c || !io.in || !io.inOffsets || !io.inSizes || !io.out.p || !io.sampleOffsets || !io.sampleCounts || !io.status)
         return PGN_ERR_INVALID_ARG;
     if (nchunks == 0) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    return launch_decode(c, codec, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts,
-                         d_status, stream, maxHint);
+    return launch_decode(c, codec, nchunks, io, stream, maxHint, CallScope::kLock);
 }
 
 int pgn_compress_batch_device(pgn_ctx* c, size_t nchunks, const int16_t* d_samples, const uint64_t* d_sample_offsets,
@@ -3202,8 +3082,8 @@ int pgn_compress_batch_device(pgn_ctx* c, size_t nchunks, const int16_t* d_sampl
                               const uint64_t* d_out_caps, uint64_t* d_out_sizes, int32_t* d_status, uint64_t* d_stats,
                               void* stream)
 {
-    return compress_batch(kCodecC5, c, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets,
-                          d_out_caps, d_out_sizes, d_status, d_stats, stream);
+    const EncIO io{d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps, d_out_sizes, d_status, d_stats};
+    return compress_batch(kCodecC5, c, nchunks, io, stream);
 }
 
 int pgn_compress_batch_device_bounded(pgn_ctx* c, uint32_t max_chunk_samples, size_t nchunks, const int16_t* d_samples,
@@ -3211,8 +3091,8 @@ int pgn_compress_batch_device_bounded(pgn_ctx* c, uint32_t max_chunk_samples, si
                                       const uint64_t* d_out_offsets, const uint64_t* d_out_caps, uint64_t* d_out_sizes,
                                       int32_t* d_status, uint64_t* d_stats, void* stream)
 {
-    return compress_batch(kCodecC5, c, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets,
-                          d_out_caps, d_out_sizes, d_status, d_stats, stream, max_chunk_samples ? max_chunk_samples : 1u);
+    const EncIO io{d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps, d_out_sizes, d_status, d_stats};
+    return compress_batch(kCodecC5, c, nchunks, io, stream, max_chunk_samples ? max_chunk_samples : 1u);
 }
 
 int pgn_decompress_batch_device_bounded(pgn_ctx* c, uint32_t max_chunk_samples, size_t nchunks, const uint8_t* d_in,
@@ -3220,16 +3100,16 @@ int pgn_decompress_batch_device_bounded(pgn_ctx* c, uint32_t max_chunk_samples, 
                                         const uint64_t* d_sample_offsets, const uint32_t* d_sample_counts,
                                         int32_t* d_status, void* stream)
 {
-    return decompress_batch(kCodecC5, c, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                            d_sample_counts, d_status, stream, max_chunk_samples ? max_chunk_samples : 1u);
+    const DecIO io{d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts, d_status};
+    return decompress_batch(kCodecC5, c, nchunks, io, stream, max_chunk_samples ? max_chunk_samples : 1u);
 }
 
 int pgn_decompress_batch_device(pgn_ctx* c, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
                                 const uint64_t* d_in_sizes, int16_t* d_samples, const uint64_t* d_sample_offsets,
                                 const uint32_t* d_sample_counts, int32_t* d_status, void* stream)
 {
-    return decompress_batch(kCodecC5, c, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                            d_sample_counts, d_status, stream);
+    const DecIO io{d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts, d_status};
+    return decompress_batch(kCodecC5, c, nchunks, io, stream);
 }
 
 int pgn_vbz_compress_batch_device(pgn_ctx* c, size_t nchunks, const int16_t* d_samples, const uint64_t* d_sample_offsets,
@@ -3237,16 +3117,16 @@ int pgn_vbz_compress_batch_device(pgn_ctx* c, size_t nchunks, const int16_t* d_s
                                   const uint64_t* d_out_caps, uint64_t* d_out_sizes, int32_t* d_status,
                                   uint64_t* d_stats, void* stream)
 {
-    return compress_batch(kCodecVbz, c, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets,
-                          d_out_caps, d_out_sizes, d_status, d_stats, stream);
+    const EncIO io{d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps, d_out_sizes, d_status, d_stats};
+    return compress_batch(kCodecVbz, c, nchunks, io, stream);
 }
 
 int pgn_vbz_decompress_batch_device(pgn_ctx* c, size_t nchunks, const uint8_t* d_in, const uint64_t* d_in_offsets,
                                     const uint64_t* d_in_sizes, int16_t* d_samples, const uint64_t* d_sample_offsets,
                                     const uint32_t* d_sample_counts, int32_t* d_status, void* stream)
 {
-    return decompress_batch(kCodecVbz, c, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                            d_sample_counts, d_status, stream);
+    const DecIO io{d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts, d_status};
+    return decompress_batch(kCodecVbz, c, nchunks, io, stream);
 }
 
 // the pgnano variants by pgn_variant id -> internal codec
@@ -3270,8 +3150,8 @@ int pgn_variant_compress_batch_device(pgn_ctx* c, int variant, size_t nchunks, c
 {
     const int codec = variant_codec(variant);
     if (codec < 0) return PGN_ERR_INVALID_ARG;
-    return compress_batch(codec, c, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets,
-                          d_out_caps, d_out_sizes, d_status, d_stats, stream);
+    const EncIO io{d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps, d_out_sizes, d_status, d_stats};
+    return compress_batch(codec, c, nchunks, io, stream);
 }
 
 int pgn_variant_decompress_batch_device(pgn_ctx* c, int variant, size_t nchunks, const uint8_t* d_in,
@@ -3281,8 +3161,8 @@ int pgn_variant_decompress_batch_device(pgn_ctx* c, int variant, size_t nchunks,
 {
     const int codec = variant_codec(variant);
     if (codec < 0) return PGN_ERR_INVALID_ARG;
-    return decompress_batch(codec, c, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets,
-                            d_sample_counts, d_status, stream);
+    const DecIO io{d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts, d_status};
+    return decompress_batch(codec, c, nchunks, io, stream);
 }
 
 }  // extern "C"
@@ -3305,36 +3185,16 @@ extern "C" int pgn_decompress_batch_device_pa(pgn_ctx* c, int codec, uint32_t ma
     // max_chunk_samples == 0: no bound (the unbounded calls, with their host wait), not a bound of 1
     const DecOut out(d_out, out_type, out_type == PGN_OUT_INT16 ? nullptr : d_cal_offset,
                      out_type == PGN_OUT_INT16 ? nullptr : d_cal_scale);
-    return decompress_batch(k, c, nchunks, d_in, d_in_offsets, d_in_sizes, out, d_out_offsets, d_sample_counts, d_status,
-                            stream, max_chunk_samples);
+    const DecIO io{d_in, d_in_offsets, d_in_sizes, out, d_out_offsets, d_sample_counts, d_status};
+    return decompress_batch(k, c, nchunks, io, stream, max_chunk_samples);
 }
 
 // ---- per-read statistics and normalised output (pgn_select.h) -----------------------------------
 static int ensure_norm(pgn_ctx* c, size_t nreads, size_t nchunks)
 {
-    if (nchunks > c->normChunks) {
-        wait_last_host(c);
-        (void)hipFree(c->normChunkOut);
-        (void)hipFree(c->normChunkRead);
-        c->normChunkOut = nullptr;
-        c->normChunkRead = nullptr;
-        c->normChunks = 0;
-        HIPCHK(hipMalloc(&c->normChunkOut, nchunks * sizeof(uint64_t)));
-        HIPCHK(hipMalloc(&c->normChunkRead, nchunks * sizeof(uint32_t)));
-        c->normChunks = nchunks;
-    }
-    if (nreads > c->normReads) {
-        wait_last_host(c);
-        (void)hipFree(c->normReadN);
-        (void)hipFree(c->normStats);
-        c->normReadN = nullptr;
-        c->normStats = nullptr;
-        c->normReads = 0;
-        HIPCHK(hipMalloc(&c->normReadN, nreads * sizeof(uint64_t)));
-        HIPCHK(hipMalloc(&c->normStats, nreads * sizeof(pgn_read_stats)));
-        c->normReads = nreads;
-    }
-    return PGN_OK;
+    int rc = reserve(c, {{c->normChunkOut, nchunks * sizeof(uint64_t)}, {c->normChunkRead, nchunks * sizeof(uint32_t)}});
+    if (rc) return rc;
+    return reserve(c, {{c->normReadN, nreads * sizeof(uint64_t)}, {c->normStats, nreads * sizeof(pgn_read_stats)}});
 }
 
 // scratch of the split selection: [SplitHead][itemFirst: slots + 1][slots], and per read the counts of
@@ -3342,30 +3202,18 @@ static int ensure_norm(pgn_ctx* c, size_t nreads, size_t nchunks)
 static int ensure_split(pgn_ctx* c, size_t nreads, sel::SplitArgs& sa)
 {
     const size_t slots = c->split.max_split_reads;
-    const auto firstBytes = [](size_t n) { return ((n + 1) * sizeof(uint32_t) + 63) & ~(size_t)63; };
-    if (slots > c->splitSlots) {
-        wait_last_host(c);
-        (void)hipFree(c->splitWork);
-        c->splitWork = nullptr;
-        c->splitSlots = 0;
-        HIPCHK(hipMalloc(&c->splitWork, 64 + firstBytes(slots) + slots * sizeof(sel::SplitSlot)));
-        c->splitSlots = slots;
-    }
-    if (nreads > c->splitReads) {
-        wait_last_host(c);
-        (void)hipFree(c->splitWholeCounts);
-        c->splitWholeCounts = nullptr;
-        c->splitReads = 0;
-        const size_t nblocks = (nreads + sel::kPlanThreads - 1) / sel::kPlanThreads;
-        HIPCHK(hipMalloc(&c->splitWholeCounts, nreads * sizeof(uint64_t) + nblocks * sizeof(sel::SplitBlock)));
-        c->splitReads = nreads;
-    }
+    const size_t firstBytes = ((slots + 1) * sizeof(uint32_t) + 63) & ~(size_t)63;
+    int rc = reserve(c, {{c->splitWork, 64 + firstBytes + slots * sizeof(sel::SplitSlot)}});
+    if (rc) return rc;
+    const size_t nblocks = (nreads + sel::kPlanThreads - 1) / sel::kPlanThreads;
+    rc = reserve(c, {{c->splitWholeCounts, nreads * sizeof(uint64_t) + nblocks * sizeof(sel::SplitBlock)}});
+    if (rc) return rc;
     static_assert(sizeof(sel::SplitHead) <= 64, "the head's room");
-    sa.head = reinterpret_cast<sel::SplitHead*>(c->splitWork);
+    sa.head = static_cast<sel::SplitHead*>(c->splitWork.p);
     sa.itemFirst = reinterpret_cast<uint32_t*>(c->splitWork + 64);
-    sa.slots = reinterpret_cast<sel::SplitSlot*>(c->splitWork + 64 + firstBytes(c->splitSlots));
+    sa.slots = reinterpret_cast<sel::SplitSlot*>(c->splitWork + 64 + firstBytes);
     sa.wholeCounts = c->splitWholeCounts;
-    sa.blocks = reinterpret_cast<sel::SplitBlock*>(c->splitWholeCounts + c->splitReads);
+    sa.blocks = reinterpret_cast<sel::SplitBlock*>(c->splitWholeCounts + nreads);
     return PGN_OK;
 }
 
@@ -3459,15 +3307,10 @@ extern "C" int pgn_read_stats_device(pgn_ctx* c, size_t nreads, const int16_t* d
     if (!c || !sel::params_valid(params)) return PGN_ERR_INVALID_ARG;
     if (!d_samples || !d_read_offsets || !d_read_counts || !d_stats) return PGN_ERR_INVALID_ARG;
     if (nreads == 0) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
     const sel::StatsArgs a{d_samples, d_read_offsets, d_read_counts, nreads, *params, d_stats, nullptr, nullptr};
-    const int rc = launch_read_stats(c, a, s);
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
-    return rc;
+    return launch_read_stats(c, a, sc.s);
 }
 
 extern "C" int pgn_decompress_reads_device_norm(pgn_ctx* c, int codec, uint32_t max_chunk_samples, size_t nreads,
@@ -3489,10 +3332,9 @@ extern "C" int pgn_decompress_reads_device_norm(pgn_ctx* c, int codec, uint32_t 
     if (out_type == PGN_OUT_F32 && !d_adc) return PGN_ERR_INVALID_ARG;  // no workspace the host could size
     if (nreads == 0) return PGN_OK;
     if (nreads > 0xFFFFFFFFull) return PGN_ERR_INVALID_ARG;  // the chunks' read index is 32-bit
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     int rc = ensure_norm(c, nreads, nchunks);
     if (rc != PGN_OK) return rc;
     hipLaunchKernelGGL(sel::expand_reads_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, s, (uint64_t)nreads,
@@ -3501,9 +3343,10 @@ extern "C" int pgn_decompress_reads_device_norm(pgn_ctx* c, int codec, uint32_t 
     HIPCHK(hipGetLastError());
     // the int16 decode, as the batch calls run it: into d_adc, or into the binary16 output itself
     int16_t* adc = d_adc ? d_adc : (int16_t*)d_out;
-    if (nchunks)
-        rc = launch_decode(c, k, nchunks, d_in, d_in_offsets, d_in_sizes, DecOut(adc), c->normChunkOut, d_sample_counts,
-                           d_chunk_status, s, max_chunk_samples);
+    if (nchunks) {
+        const DecIO io{d_in, d_in_offsets, d_in_sizes, adc, c->normChunkOut, d_sample_counts, d_chunk_status};
+        rc = launch_decode(c, k, nchunks, io, s, max_chunk_samples, CallScope::kLocked);
+    }
     if (rc != PGN_OK) return rc;
     pgn_read_stats* stats = d_stats ? d_stats : c->normStats;
     const sel::StatsArgs a{adc, d_read_out_offsets, c->normReadN, nreads, *params, stats, nchunks ? d_chunk_status : nullptr,
@@ -3518,8 +3361,6 @@ extern "C" int pgn_decompress_reads_device_norm(pgn_ctx* c, int codec, uint32_t 
             hipLaunchKernelGGL(sel::norm_convert_kernel<_Float16>, grid, dim3(256), 0, s, na);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return rc;
 }
 
@@ -3528,18 +3369,7 @@ static int ensure_reads_pa(pgn_ctx* c, size_t nchunks)
 {
     int rc = ensure_norm(c, 0, nchunks);  // normChunkOut (and the norm call's other per-chunk array)
     if (rc != PGN_OK) return rc;
-    if (nchunks > c->paChunks) {
-        wait_last_host(c);
-        (void)hipFree(c->paChunkOffset);
-        (void)hipFree(c->paChunkScale);
-        c->paChunkOffset = nullptr;
-        c->paChunkScale = nullptr;
-        c->paChunks = 0;
-        HIPCHK(hipMalloc(&c->paChunkOffset, nchunks * sizeof(float)));
-        HIPCHK(hipMalloc(&c->paChunkScale, nchunks * sizeof(float)));
-        c->paChunks = nchunks;
-    }
-    return PGN_OK;
+    return reserve(c, {{c->paChunkOffset, nchunks * sizeof(float)}, {c->paChunkScale, nchunks * sizeof(float)}});
 }
 
 static int launch_reads_status(size_t nreads, const uint64_t* d_first, const int32_t* d_chunk_status, int32_t* d_read_status,
@@ -3567,10 +3397,9 @@ extern "C" int pgn_decompress_reads_device_pa(pgn_ctx* c, int codec, uint32_t ma
     if (nchunks && (!d_in || !d_in_offsets || !d_in_sizes || !d_sample_counts || !d_chunk_status)) return PGN_ERR_INVALID_ARG;
     const bool cal = out_type != PGN_OUT_INT16;
     if (cal && (!d_read_cal_offset || !d_read_cal_scale)) return PGN_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     int rc = PGN_OK;
     if (nchunks) {
         rc = ensure_reads_pa(c, nchunks);
@@ -3582,13 +3411,11 @@ extern "C" int pgn_decompress_reads_device_pa(pgn_ctx* c, int codec, uint32_t ma
         HIPCHK(hipGetLastError());
         // the decode of pgn_decompress_batch_device_pa, with the expanded arrays
         const DecOut out(d_out, out_type, cal ? c->paChunkOffset : nullptr, cal ? c->paChunkScale : nullptr);
-        rc = launch_decode(c, k, nchunks, d_in, d_in_offsets, d_in_sizes, out, c->normChunkOut, d_sample_counts,
-                           d_chunk_status, s, max_chunk_samples);
+        const DecIO io{d_in, d_in_offsets, d_in_sizes, out, c->normChunkOut, d_sample_counts, d_chunk_status};
+        rc = launch_decode(c, k, nchunks, io, s, max_chunk_samples, CallScope::kLocked);
         if (rc != PGN_OK) return rc;
     }
     if (d_read_status) rc = launch_reads_status(nreads, d_read_first_chunk, d_chunk_status, d_read_status, s);
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return rc;
 }
 
@@ -3597,14 +3424,9 @@ extern "C" int pgn_reads_status_device(pgn_ctx* c, size_t nreads, const uint64_t
 {
     if (!c || !d_read_first_chunk || !d_read_status) return PGN_ERR_INVALID_ARG;
     if (nreads == 0) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
-    const int rc = launch_reads_status(nreads, d_read_first_chunk, d_chunk_status, d_read_status, s);
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
-    return rc;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    return launch_reads_status(nreads, d_read_first_chunk, d_chunk_status, d_read_status, sc.s);
 }
 
 // ---- trimmed, normalised model segments (pgn_segment.h) -----------------------------------------
@@ -3619,16 +3441,10 @@ struct SegWork {
 
 static int ensure_segment(pgn_ctx* c, size_t nreads, SegWork& w)
 {
-    if (nreads > c->segReads) {
-        wait_last_host(c);
-        (void)hipFree(c->segWork);
-        c->segWork = nullptr;
-        c->segReads = 0;
-        HIPCHK(hipMalloc(&c->segWork, nreads * (3 * sizeof(uint64_t) + 2 * sizeof(pgn_read_stats)) + sizeof(uint64_t)));
-        c->segReads = nreads;
-    }
-    const size_t R = c->segReads;
-    w.headN = reinterpret_cast<uint64_t*>(c->segWork);
+    const int rc = reserve(c, {{c->segWork, nreads * (3 * sizeof(uint64_t) + 2 * sizeof(pgn_read_stats)) + sizeof(uint64_t)}});
+    if (rc) return rc;
+    const size_t R = nreads;
+    w.headN = static_cast<uint64_t*>(c->segWork.p);
     w.trimOffsets = w.headN + R;
     w.trimCounts = w.trimOffsets + R;
     w.headStats = reinterpret_cast<pgn_read_stats*>(w.trimCounts + R);
@@ -3654,10 +3470,9 @@ extern "C" int pgn_segment_reads_device(pgn_ctx* c, size_t nreads, const int16_t
         if (nreads > 0xFFFFFFFFull) return PGN_ERR_INVALID_ARG;  // a segment's read index is 32-bit
     }
     if (nreads == 0 && !d_total) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     if (nreads == 0) {
         HIPCHK(hipMemsetAsync(d_total, 0, sizeof(uint64_t), s));
         return PGN_OK;
@@ -3715,23 +3530,13 @@ extern "C" int pgn_segment_reads_device(pgn_ctx* c, size_t nreads, const int16_t
             hipLaunchKernelGGL(seg::segment_write_kernel<_Float16>, grid, dim3(seg::kWriteThreads), 0, s, wa);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return PGN_OK;
 }
 
 // ---- model output back to reads (pgn_stitch.h) ----------------------------------------------------
 static int ensure_stitch(pgn_ctx* c, size_t nblocks)
 {
-    if (nblocks > c->stitchBlocks) {
-        wait_last_host(c);
-        (void)hipFree(c->stitchSums);
-        c->stitchSums = nullptr;
-        c->stitchBlocks = 0;
-        HIPCHK(hipMalloc(&c->stitchSums, (nblocks + 1) * sizeof(uint64_t)));
-        c->stitchBlocks = nblocks;
-    }
-    return PGN_OK;
+    return reserve(c, {{c->stitchSums, (nblocks + 1) * sizeof(uint64_t)}});
 }
 
 extern "C" int pgn_stitch_plan_device(pgn_ctx* c, size_t nreads, const pgn_read_segments* d_reads,
@@ -3748,10 +3553,9 @@ extern "C" int pgn_stitch_plan_device(pgn_ctx* c, size_t nreads, const pgn_read_
         if (nreads > 0xFFFFFFFFull) return PGN_ERR_INVALID_ARG;  // a segment's read index is 32-bit
         if (segment_capacity >> 40) return PGN_ERR_INVALID_ARG;  // the count kernel's grid
     }
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     if (nreads == 0) {
         HIPCHK(hipMemsetAsync(d_read_frames, 0, sizeof(uint64_t), s));
         return PGN_OK;
@@ -3769,8 +3573,6 @@ extern "C" int pgn_stitch_plan_device(pgn_ctx* c, size_t nreads, const pgn_read_
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(stitch::stitch_read_frames_kernel, dim3((unsigned)(nreads / 256 + 1)), dim3(256), 0, s, pa);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return PGN_OK;
 }
 
@@ -3787,10 +3589,9 @@ extern "C" int pgn_stitch_rows_device(pgn_ctx* c, const pgn_stitch_params* param
     if (nsegments == 0) return PGN_OK;
     if (!d_plan || !d_rows || !d_out) return PGN_ERR_INVALID_ARG;
     if (out_capacity_frames == 0) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     // a piece (a dense row's kept frames, or one frame of a strided row) is shared by the smallest power of
     // two of threads that covers its 16-byte units -- its bytes, up to 32, where the destination is not known
     // to fall on 16-byte boundaries -- up to the workgroup
@@ -3811,42 +3612,25 @@ extern "C" int pgn_stitch_rows_device(pgn_ctx* c, const pgn_stitch_params* param
                               out_capacity_frames, log2Tpr, dense ? 1u : 0u};
     hipLaunchKernelGGL(stitch::stitch_rows_kernel, grid, dim3(stitch::kRowsThreads), 0, s, ra);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return PGN_OK;
 }
 
 // ---- stitched frames to bases (pgn_ctc.h) -----------------------------------------------------------
 static int ensure_ctc(pgn_ctx* c, size_t ntiles, size_t codeBytes)
 {
-    if (ntiles > c->ctcTiles) {
-        wait_last_host(c);
-        (void)hipFree(c->ctcSums);
-        c->ctcSums = nullptr;
-        c->ctcTiles = 0;
-        // the tiles' sums, the edges' reads, the spans' sums and the total
-        HIPCHK(hipMalloc(&c->ctcSums, ((ntiles + 1) * 2 + ntiles / ctc::kScanSpan + 2) * sizeof(uint64_t)));
-        c->ctcTiles = ntiles;
-    }
-    if (codeBytes > c->ctcCodeBytes) {
-        wait_last_host(c);
-        (void)hipFree(c->ctcCodes);
-        c->ctcCodes = nullptr;
-        c->ctcCodeBytes = 0;
-        HIPCHK(hipMalloc(&c->ctcCodes, codeBytes));
-        c->ctcCodeBytes = codeBytes;
-    }
-    return PGN_OK;
+    // the tiles' sums, the edges' reads, the spans' sums and the total
+    int rc = reserve(c, {{c->ctcSums, ((ntiles + 1) * 2 + ntiles / ctc::kScanSpan + 2) * sizeof(uint64_t)}});
+    if (rc) return rc;
+    return reserve(c, {{c->ctcCodes, codeBytes}});
 }
 
 // what the two calls share once their arguments are checked: the label pass (decode) or the count of the
 // caller's codes (collapse), the scan, the write pass and the statuses
 static int ctc_run(pgn_ctx* c, ctc::Args& a, bool decode, bool ownCodes, void* stream)
 {
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     if (a.nreads == 0) {
         HIPCHK(hipMemsetAsync(a.readBases, 0, sizeof(uint64_t), s));
         return PGN_OK;
@@ -3856,8 +3640,8 @@ static int ctc_run(pgn_ctx* c, ctc::Args& a, bool decode, bool ownCodes, void* s
     const int rc = ensure_ctc(c, (size_t)a.ntiles, ownCodes ? (size_t)a.capacity : 0);
     if (rc != PGN_OK) return rc;
     a.tileSums = c->ctcSums;
-    a.bounds = reinterpret_cast<uint32_t*>(c->ctcSums + c->ctcTiles + 1);
-    a.spanSums = c->ctcSums + 2 * (c->ctcTiles + 1);
+    a.bounds = reinterpret_cast<uint32_t*>(c->ctcSums + a.ntiles + 1);
+    a.spanSums = c->ctcSums + 2 * (a.ntiles + 1);
     a.nspans = (a.ntiles + ctc::kScanSpan - 1) / ctc::kScanSpan;
     if (ownCodes) a.codes = c->ctcCodes;
     const dim3 grid((unsigned)a.ntiles), block(ctc::kThreads);
@@ -3880,8 +3664,6 @@ static int ctc_run(pgn_ctx* c, ctc::Args& a, bool decode, bool ownCodes, void* s
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(ctc::ctc_status_kernel, dim3((unsigned)(a.nreads / 256 + 1)), dim3(256), 0, s, a);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return PGN_OK;
 }
 
@@ -3967,10 +3749,9 @@ int pgn_norm_decoded_reads(pgn_ctx* c, size_t nreads, size_t nchunks, const int1
 {
     if (!c || !sel::params_valid(params) || (out_type != PGN_OUT_F32 && out_type != PGN_OUT_F16)) return PGN_ERR_INVALID_ARG;
     if (nreads == 0) return PGN_OK;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (c->haveLast) HIPCHK(hipStreamWaitEvent(s, c->evLast, 0));
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
     int rc = ensure_norm(c, nreads, 0);
     if (rc != PGN_OK) return rc;
     pgn_read_stats* stats = d_stats ? d_stats : c->normStats;
@@ -3985,8 +3766,6 @@ int pgn_norm_decoded_reads(pgn_ctx* c, size_t nreads, size_t nchunks, const int1
             hipLaunchKernelGGL(sel::norm_convert_kernel<_Float16>, grid, dim3(256), 0, s, na);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(c->evLast, s));
-    c->haveLast = true;
     return rc;
 }
 
@@ -3997,8 +3776,8 @@ int pgn_compress_batch_bounded(pgn_ctx* c, int codec, uint32_t max_samples, size
 {
     const int k = bounded_codec(codec);
     if (k < 0) return PGN_ERR_INVALID_ARG;
-    return compress_batch(k, c, nchunks, d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps,
-                          d_out_sizes, d_status, d_stats, stream, max_samples);
+    const EncIO io{d_samples, d_sample_offsets, d_sample_counts, d_out, d_out_offsets, d_out_caps, d_out_sizes, d_status, d_stats};
+    return compress_batch(k, c, nchunks, io, stream, max_samples);
 }
 
 int pgn_decompress_batch_bounded(pgn_ctx* c, int codec, uint32_t max_samples, size_t nchunks, const uint8_t* d_in,
@@ -4008,8 +3787,8 @@ int pgn_decompress_batch_bounded(pgn_ctx* c, int codec, uint32_t max_samples, si
 {
     const int k = bounded_codec(codec);
     if (k < 0) return PGN_ERR_INVALID_ARG;
-    return decompress_batch(k, c, nchunks, d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts,
-                            d_status, stream, max_samples);
+    const DecIO io{d_in, d_in_offsets, d_in_sizes, d_samples, d_sample_offsets, d_sample_counts, d_status};
+    return decompress_batch(k, c, nchunks, io, stream, max_samples);
 }
 
 extern "C" {
@@ -4119,18 +3898,20 @@ int pgn_synth_reads_device(pgn_ctx* c, size_t nreads, uint64_t seed, uint64_t fi
 // ---- host-memory per-chunk entry points (the plugin surface) --------------------------------
 static int ensure_stage(pgn_ctx* c, size_t bytes)
 {
-    if (bytes <= c->stageBytes) return PGN_OK;
-    wait_last_host(c);
-    (void)hipFree(c->stage);
+    if (c->hstage && bytes <= c->stage.cap) return PGN_OK;
+    const size_t b = align_up(bytes > c->stage.cap ? bytes : c->stage.cap, 1 << 20);
+    const int rc = reserve(c, {{c->stage, b}});  // after its wait nothing uses the pinned mirror either
+    if (rc) return rc;
     if (c->hstage) (void)hipHostFree(c->hstage);
-    c->stage = nullptr;
     c->hstage = nullptr;
-    c->stageBytes = 0;
-    size_t b = align_up(bytes, 1 << 20);
-    HIPCHK(hipMalloc(&c->stage, b));
-    HIPCHK(hipHostMalloc((void**)&c->hstage, b, hipHostMallocDefault));
-    HIPCHK(hipHostGetDevicePointer((void**)&c->hstageDev, c->hstage, 0));
-    c->stageBytes = b;
+    uint8_t* h = nullptr;
+    HIPCHK(hipHostMalloc((void**)&h, b, hipHostMallocDefault));
+    const hipError_t e = hipHostGetDevicePointer((void**)&c->hstageDev, h, 0);
+    if (e != hipSuccess) {
+        (void)hipHostFree(h);
+        return hip_fail(e, "hipHostGetDevicePointer");
+    }
+    c->hstage = h;
     return PGN_OK;
 }
 
@@ -4163,8 +3944,8 @@ static int compress_signal_one(int codec, pgn_ctx* c, const int16_t* samples, si
     if (n) memcpy(c->hstage + hdrB, samples, 2 * n);
     HIPCHK(hipMemcpyAsync(dh, c->hstage, hdrB + 2 * n, hipMemcpyHostToDevice, c->stream));
     StageHdr* d = (StageHdr*)dh;
-    rc = launch_encode(c, codec, 1, (const int16_t*)din, &d->off0, &d->count, hout, &d->outOff, &d->outCap,
-                       &hd->outSize, &hd->status, hd->stats, c->stream, n ? (uint32_t)n : 1u);
+    const EncIO io{(const int16_t*)din, &d->off0, &d->count, hout, &d->outOff, &d->outCap, &hd->outSize, &hd->status, hd->stats};
+    rc = launch_encode(c, codec, 1, io, c->stream, n ? (uint32_t)n : 1u, CallScope::kLocked);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     *out_size = (size_t)hh->outSize;
@@ -4191,15 +3972,14 @@ static int decompress_signal_one(int codec, pgn_ctx* c, const uint8_t* src, size
     if (len) memcpy(c->hstage + hdrB, src, len);
     HIPCHK(hipMemcpyAsync(dh, c->hstage, hdrB + len, hipMemcpyHostToDevice, c->stream));
     StageHdr* d = (StageHdr*)dh;
-    rc = launch_decode(c, codec, 1, din, &d->inOff, &d->inSize, hout, &d->off0, &d->count, &hd->status, c->stream,
-                       n ? (uint32_t)n : 1u);
+    const DecIO io{din, &d->inOff, &d->inSize, hout, &d->off0, &d->count, &hd->status};
+    rc = launch_decode(c, codec, 1, io, c->stream, n ? (uint32_t)n : 1u, CallScope::kLocked);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     if (hh->status == PGN_ERR_UNSUPPORTED) {  // frames claiming more than the intermediate: the claims pass
         const uint8_t* bl = c->hstage + hdrB;
         const uint64_t ln = len;
-        rc = claims_from_host(c, codec, 1, &hh->status, &hh->count, &bl, &ln, din, &d->inOff, &d->inSize, hout, &d->off0,
-                              &d->count, &hd->status, c->stream);
+        rc = claims_from_host(c, codec, 1, &hh->status, &hh->count, &bl, &ln, io, c->stream);
         if (rc) return rc;
     }
     if (hh->status != PGN_OK) return hh->status;
@@ -4263,6 +4043,14 @@ static void pc_run(pgn_ctx* c, PcArena& A)
     PcHdr* ho = (PcHdr*)A.hDev;           // results straight into pinned memory
     uint8_t* const inD = A.d + kPcHdr;
     uint8_t* const outH = A.hDev + kPcHdr + kPcInCap;
+    // the arrays of the group of requests that starts at request i0
+    const auto encIO = [&](int i0) {
+        return EncIO{(const int16_t*)inD, dh->off0 + i0, dh->cnt + i0, outH, dh->outOff + i0, dh->outCap + i0,
+                     ho->outSize + i0, ho->status + i0, ho->stats + (size_t)i0 * PGN_STATS_PER_CHUNK};
+    };
+    const auto decIO = [&](int i0) {
+        return DecIO{inD, dh->inOff + i0, dh->inSize + i0, (int16_t*)outH, dh->off0 + i0, dh->cnt + i0, ho->status + i0};
+    };
     int rc = PGN_OK;
     {
         std::lock_guard<std::mutex> g(c->mu);
@@ -4277,13 +4065,8 @@ static void pc_run(pgn_ctx* c, PcArena& A)
                 i1++;
             }
             const size_t m = (size_t)(i1 - i0);
-            if (ord[i0]->dir == 0)
-                rc = launch_encode(c, ord[i0]->codec, m, (const int16_t*)inD, dh->off0 + i0, dh->cnt + i0, outH,
-                                   dh->outOff + i0, dh->outCap + i0, ho->outSize + i0, ho->status + i0,
-                                   ho->stats + (size_t)i0 * PGN_STATS_PER_CHUNK, c->stream, maxN);
-            else
-                rc = launch_decode(c, ord[i0]->codec, m, inD, dh->inOff + i0, dh->inSize + i0, (int16_t*)outH,
-                                   dh->off0 + i0, dh->cnt + i0, ho->status + i0, c->stream, maxN);
+            if (ord[i0]->dir == 0) rc = launch_encode(c, ord[i0]->codec, m, encIO(i0), c->stream, maxN, CallScope::kLocked);
+            else rc = launch_decode(c, ord[i0]->codec, m, decIO(i0), c->stream, maxN, CallScope::kLocked);
             i0 = i1;
         }
         if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PGN_OK) rc = PGN_ERR_HIP;
@@ -4298,9 +4081,8 @@ static void pc_run(pgn_ctx* c, PcArena& A)
                     bl[i - i0] = A.h + kPcHdr + ord[i]->inOff;
                     ln[i - i0] = ord[i]->inBytes;
                 }
-                rc = claims_from_host(c, ord[i0]->codec, (size_t)(i1 - i0), hh->status + i0, hh->cnt + i0, bl, ln, inD,
-                                      dh->inOff + i0, dh->inSize + i0, (int16_t*)outH, dh->off0 + i0, dh->cnt + i0,
-                                      ho->status + i0, c->stream);
+                rc = claims_from_host(c, ord[i0]->codec, (size_t)(i1 - i0), hh->status + i0, hh->cnt + i0, bl, ln, decIO(i0),
+                                      c->stream);
             }
             i0 = i1;
         }
