@@ -106,6 +106,49 @@ __device__ __forceinline__ void nwin_flush(uint8_t* W, uint32_t& fill, uint8_t* 
     fill = tail;
 }
 
+// The same two flushes for the full steps of c5_split_wave, as exactly one 16-byte store per lane
+// and nothing branched around it.  gfx9 counts loads and stores on one in-order counter, and the
+// compiler leaves younger operations in flight across a wait only when every path issues the same
+// number of them; with a per-lane loop of 0..1 stores the next step's wait for its prefetched
+// samples became vmcnt(0), that is a wait for this step's stores to be acknowledged.  A full step
+// completes at most 64 M blocks (fill <= 15 + 1024) and 32 S blocks, so lane b stores block
+// min(b, nblk): the lanes at and above nblk all store the window's incomplete block at the
+// stream's end, out + gpos + 16 nblk.  Those bytes lie past what the stream holds so far, inside
+// its capacity plus padding (stream_pad: 64 bytes), and the next flush or the tail loop writes
+// them again with their final values (a wave's stores to one address are performed in order).
+__device__ __forceinline__ void bwin_flush_fixed(uint8_t* W, uint32_t& fill, uint8_t* out, uint32_t& gpos)
+{
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t nblk = fill >> 4, tail = fill & 15u;
+    const uint32_t b = lane < nblk ? lane : nblk;
+    gst<uint4>(out + gpos + 16u * b, *(const uint4*)(W + 16u * b));
+    if (nblk) {
+        const uint8_t v = W[16u * nblk + (lane & 15u)];
+        if (lane < tail) W[lane] = v;
+    }
+    gpos += 16u * nblk;
+    fill = tail;
+}
+__device__ __forceinline__ void nwin_flush_fixed(uint8_t* W, uint32_t& fill, uint8_t* out, uint32_t& gpos)
+{
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t nblk = fill >> 5, tail = fill & 31u;
+    const uint32_t b = lane < nblk ? lane : nblk;
+    const uint4 a = *(const uint4*)(W + 32u * b), c = *(const uint4*)(W + 32u * b + 16u);
+    uint4 o;
+    o.x = pack_nibbles(a.x) | (pack_nibbles(a.y) << 16);
+    o.y = pack_nibbles(a.z) | (pack_nibbles(a.w) << 16);
+    o.z = pack_nibbles(c.x) | (pack_nibbles(c.y) << 16);
+    o.w = pack_nibbles(c.z) | (pack_nibbles(c.w) << 16);
+    gst<uint4>(out + gpos + 16u * b, o);
+    if (nblk) {
+        const uint8_t v = W[32u * nblk + (lane & 31u)];
+        if (lane < tail) W[lane] = v;
+    }
+    gpos += 16u * nblk;
+    fill = tail;
+}
+
 // Class offsets: C5 (N01) stores v-1 / v-17 / v-273 (C5.hpp:105-140); C4 (N02, C4.hpp:100-133)
 // stores the raw value, classes v < 16 / v < 256 / else.
 template <bool C4> struct ClassOffsets {
@@ -249,21 +292,45 @@ __device__ __forceinline__ void c5_split_wave(const int16_t* __restrict__ x, uin
     // the samples of a full step are loaded one step ahead, so their latency overlaps a step
     uint4 na = make_uint4(0u, 0u, 0u, 0u), nb = na;
     auto ld16 = [&](const int16_t* p) { return gld<uint4>(p); };
-    if (kSplitStep <= n) {
+    const uint32_t nfull = n & ~(kSplitStep - 1u);
+    if (nfull) {
         na = ld16(x + 16u * lane);
         nb = ld16(x + 16u * lane + 8);
+        // The first step's wait sees what follows the loads here, every later one what follows them
+        // in a step, and the compiler waits for the smaller of the two counts.  So the same three
+        // stores follow here: the key words of step 0 and the first S and M blocks, all written
+        // again with their values by step 0's key store and by the first flushes or the tails.
+        gst<uint32_t>(st.K + 4u * lane, 0u);
+        gst<uint4>(st.S, make_uint4(0u, 0u, 0u, 0u));
+        gst<uint4>(st.M, make_uint4(0u, 0u, 0u, 0u));
     }
-    for (uint32_t t = 0; t < n; t += kSplitStep) {
-        const bool full = t + kSplitStep <= n;
+    // Full steps: the same memory operations in the same order every step -- the two prefetch loads,
+    // then the rare class-3 flushes, then the key-word store and one S and one M store per lane --
+    // so the next step's wait for its samples leaves this step's three stores in flight (see
+    // bwin_flush_fixed).  The prefetch of the last full step reads that step again, not past it.
+    uint32_t t = 0;
+    for (; t < nfull; t += kSplitStep) {
         const uint4 ca = na, cb = nb;
-        if (t + 2 * kSplitStep <= n) {
-            na = ld16(x + t + kSplitStep + 16u * lane);
-            nb = ld16(x + t + kSplitStep + 16u * lane + 8);
-        }
-        const uint32_t kw = full ? split_step<true, C4>(ca, cb, x, n, t, W, fS, fM, fL, prevX)
-                                 : split_step<false, C4>(ca, cb, x, n, t, W, fS, fM, fL, prevX);
+        const uint32_t tn = t + 2 * kSplitStep <= n ? t + kSplitStep : t;
+        na = ld16(x + tn + 16u * lane);
+        nb = ld16(x + tn + 16u * lane + 8);
+        const uint32_t kw = split_step<true, C4>(ca, cb, x, n, t, W, fS, fM, fL, prevX);
         fH = fL;
-        const uint32_t nK = full ? kSplitStep / 4 : (n - t + 3) / 4;
+        lds_sync();
+        if (fL >= 16) {  // class 3 is rare; issued before the fixed stores, so only these are waited for
+            bwin_flush(W.L, fL, st.Ll, gL);
+            bwin_flush(W.H, fH, st.Lh, gH);
+        }
+        gst<uint32_t>(st.K + (t >> 2) + 4u * lane, kw);
+        nwin_flush_fixed(W.S, fS, st.S, gS);
+        bwin_flush_fixed(W.M, fM, st.M, gM);
+        lds_sync();
+    }
+    if (t < n) {  // the ragged last step
+        const uint4 ca = na, cb = nb;
+        const uint32_t kw = split_step<false, C4>(ca, cb, x, n, t, W, fS, fM, fL, prevX);
+        fH = fL;
+        const uint32_t nK = (n - t + 3) / 4;
         uint8_t* kout = st.K + (t >> 2);
         if (4u * lane + 4u <= nK) gst<uint32_t>(kout + 4u * lane, kw);
         else for (uint32_t b = 4u * lane; b < nK; b++) gst<uint8_t>(kout + b, (uint8_t)(kw >> (8u * (b - 4u * lane))));

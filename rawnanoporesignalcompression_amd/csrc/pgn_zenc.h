@@ -663,8 +663,10 @@ __device__ __noinline__ SearchOut fast_search_wave(const uint8_t* __restrict__ s
 // Huffman bit packing of one segment: symbols are written last-to-first (HUF_compress1X order), so
 // emission r takes symbol src[len-1-r] and its bit position is the sum of the code lengths emitted
 // before it.  A step emits 1024 symbols, 16 per lane from one 16-byte load; lane code groups are
-// OR-ed into an LDS bit window at their prefix-sum offsets, and the window's complete words leave
-// as coalesced dword stores.
+// OR-ed into an LDS bit window at their prefix-sum offsets, and the window's complete 16-byte quads
+// leave as two stores per lane (the ragged last step: complete words as dword stores).  The store
+// count of a full step is fixed so that the wait for the next step's prefetched block leaves the
+// stores in flight (one in-order counter covers loads and stores; see bwin_flush_fixed, pgn_c5.h).
 // ---------------------------------------------------------------------------------------------
 __device__ __noinline__ void huf_encode_segment_wave(uint8_t* __restrict__ out, const uint8_t* __restrict__ src, uint32_t len,
                                                      uint32_t totalBits, lds_u32* win)
@@ -691,7 +693,9 @@ __device__ __noinline__ void huf_encode_segment_wave(uint8_t* __restrict__ out, 
         if (FULL || a >= 0) {
             const uint4 v = nv;
             wv[0] = v.x; wv[1] = v.y; wv[2] = v.z; wv[3] = v.w;
-            if (a - 1024 >= 0) nv = gld<uint4>(src + (a - 1024));
+            // full steps load unconditionally (a lane without a next block reads the segment's start)
+            if (FULL) nv = gld<uint4>(src + (a - 1024 >= 0 ? a - 1024 : 0));
+            else if (a - 1024 >= 0) nv = gld<uint4>(src + (a - 1024));
         } else {
 #pragma unroll
             for (int q = 0; q < 4; q++) {
@@ -744,6 +748,29 @@ __device__ __noinline__ void huf_encode_segment_wave(uint8_t* __restrict__ out, 
         const uint32_t endRel = bitBase + stepBits - winLo;
         const uint32_t complete = endRel >> 5;
         uint8_t* o = out + (winLo >> 3);
+        if (FULL) {
+            // A fixed number of stores per step, nothing branched around them: the window's complete
+            // 16-byte quads leave as two stores per lane (a step completes at most 352 + 3 words, 88
+            // quads), a lane past the last complete quad stores that quad again (same bytes, same
+            // address), and the words behind it (up to three complete ones and the partial one) move
+            // to the front.  No byte past the complete words is written (nq >= 8: each of a full step's
+            // 1,024 symbols has a code of one bit or more).
+            const uint32_t nq = complete >> 2, last = nq ? nq - 1u : 0u;
+            const uint32_t keep = lane < 4 ? win[4 * nq + lane] : 0u;
+            const uint32_t q0 = lane < last ? lane : last, q1 = lane + 64 < last ? lane + 64 : last;
+            const uint4 v0 = make_uint4(win[4 * q0], win[4 * q0 + 1], win[4 * q0 + 2], win[4 * q0 + 3]);
+            const uint4 v1 = make_uint4(win[4 * q1], win[4 * q1 + 1], win[4 * q1 + 2], win[4 * q1 + 3]);
+            gst<uint4>(o + 16 * q0, v0);
+            gst<uint4>(o + 16 * q1, v1);
+            lds_sync();
+            for (uint32_t w = lane; w <= complete; w += 64) win[w] = 0u;
+            lds_sync();
+            if (lane < 4) win[lane] = keep;
+            lds_sync();
+            winLo += nq * 128;
+            bitBase += stepBits;
+            return;
+        }
         // complete words leave and are cleared in one pass; the partial word moves to the front
         const uint32_t carry = win[complete];
         for (uint32_t w = lane; w <= complete; w += 64) {
@@ -2199,7 +2226,10 @@ __device__ __noinline__ size_t zstd1_compress_wave(uint8_t* __restrict__ dst, co
             const size_t litSize = uni(lo.size);
             wave_sync();
             if (nbSeq == 0) {
-                if (lane == 0) body[litSize] = 0;
+                // the "no sequences" byte, only where the block stays compressed (the test below): a
+                // block that turns raw ends at body + bs, before this byte -- which then lay past the
+                // blob's size when the frame was the chunk's last
+                if (lane == 0 && litSize + 1 < maxCSize) body[litSize] = 0;
                 seqSize = 1;
             } else {
                 P.count(10);
