@@ -591,8 +591,7 @@ int pgn_stitch_rows_device(pgn_ctx *ctx, const pgn_stitch_params *params, const 
  * element size; nreads >= 2^32 or frame_capacity >= 2^40; a NULL d_read_bases; with nreads > 0 a NULL
  * d_read_frames or d_read_status; with frame_capacity > 0 a NULL d_frames (d_codes in the collapse call); with
  * base_capacity > 0 a NULL d_seq.  With nreads == 0 only d_read_bases[0] = 0 is written.
- * Not covered: CRF or transducer decoding and beam search; quality strings (phred calibration); decoding the
- * rows before stitching; bfloat16 scores. */
+ * Not covered: transducer decoding and beam search; quality strings (phred calibration); bfloat16 scores. */
 #define PGN_CTC_TILE_FRAMES 1024
 typedef struct pgn_ctc_params {
     uint32_t classes;       /* C, 2..64 */
@@ -614,6 +613,79 @@ int pgn_collapse_codes_device(pgn_ctx *ctx, const uint8_t alphabet[128], size_t 
                               uint64_t frame_capacity,
                               uint8_t *d_seq, uint64_t base_capacity, uint64_t *d_read_bases, int32_t *d_read_status,
                               uint32_t *d_base_frame /* may be NULL */, void *stream);
+
+/* ---- Model rows to per-frame codes (CRF) ---------------------------------------------------------------
+ * The best-path (Viterbi) decode of a CRF model's output, row by row as the model wrote it and before any
+ * stitching: one code byte per frame, exactly the byte pgn_collapse_codes_device reads, so that
+ *   segment -> model -> this call -> pgn_stitch_rows_device (frame_bytes = 1) -> pgn_collapse_codes_device
+ * is a route to bases.  Every output is a selection among float32 sums formed in a fixed order, so the
+ * tolerance is zero.  No outside source defines the rule, so this text does.
+ *
+ * Parameters (pgn_crf_params, 16 bytes): k = state_len in 1..5, so S = 4^k states; transitions is 5 or 4 and
+ * C = transitions * S; score_type is PGN_OUT_F16 or PGN_OUT_F32, and float16 is used as its exact float32
+ * value.  A state is a k-mer in base 4; its last digit s & 3 is the newest base.  The predecessor of s by
+ * option b in 0..3 is
+ *   p(s, b) = (b * S + s) >> 2      (drop s's newest base and put b on top).
+ * Scores of frame t are x_t[0..C).  With transitions == 5, x_t[5s] is "stay in s" and x_t[5s + 1 + b] is
+ * "move into s from p(s, b)".  With transitions == 4 the move score is x_t[4s + b] and every stay scores the
+ * constant stay_score (models with a fixed blank score).  With transitions == 5, stay_score must be +0.0f
+ * (bits zero): its role is that of a pad.
+ *
+ * Forward, all arithmetic in float32, one rounding per add:
+ *   a_0[s] = 0.
+ *   For t = 0..T-1 and every s:
+ *     best = a_t[s] + stay, j = 0.
+ *     For b = 0, 1, 2, 3 in that order: cand = a_t[p(s, b)] + move(t, s, b);
+ *       if (cand > best) { best = cand; j = 1 + b; }
+ *     a_{t+1}[s] = best, bp_t[s] = j.
+ * The comparison is that C expression and nothing else.  A tie keeps the earlier option.  A NaN candidate
+ * never replaces, and a NaN best is never replaced.
+ * End: e = 0, m = a_T[0].  For s = 1..S-1: if (a_T[s] > m) { m = a_T[s]; e = s; }.  row_score = m, s_T = e.
+ * Traceback, for t = T-1 .. 0:
+ *   j = bp_t[s_{t+1}].
+ *   code_t = (s_{t+1} & 3) | (j ? 0x80 : 0).
+ *   s_t = j ? p(s_{t+1}, j - 1) : s_{t+1}.
+ * code_t is the byte the collapse call reads: bit 7 is the move, the class below it is the base, and the
+ * alphabet is "ACGT".  The first state's older bases are never emitted.  A joint between two rows may double or
+ * lose a base there, as with any chunked decode; stitching cuts in the middle of the overlap for that reason.
+ *
+ * pgn_crf_viterbi_rows_device: frame t of row g is the C contiguous elements at
+ *   d_rows + g * row_stride_bytes + t * frame_stride_bytes
+ * (the convention of pgn_stitch_rows_device: it serves [N, T, C] and [T, N, C]), and row g's codes go to
+ * d_codes + g * codes_row_stride + t.  The call is asynchronous on `stream` with no host wait.  Nothing but the
+ * T code bytes per row and d_row_score[g] is written.  Any element-aligned pointer and strides are allowed;
+ * 16-byte loads are used where the address allows them, and no byte outside the frames is read.
+ *
+ * Scratch is the backpointers; they live on the context:
+ *   bytes per row = 4 * S * ceil(T / 8) + 16
+ * (4 bits per state and frame, a dword per state and 8 frames, then the row's end state).
+ * pgn_ctx_set_crf_scratch(ctx, bytes) sets a cap on it; the default is PGN_CRF_DEFAULT_SCRATCH (1 GiB) and 0
+ * restores it.  The rows of one call are handled in successive groups of floor(cap / bytes per row) rows; the
+ * groups are further launches on the same stream, with no host wait.  A single row that does not fit the cap is
+ * PGN_ERR_INVALID_ARG.
+ *
+ * PGN_ERR_INVALID_ARG before any GPU call, checking in this order: a NULL ctx or params; state_len outside
+ * 1..5, transitions not 4 or 5, score_type not PGN_OUT_F32 or PGN_OUT_F16, or stay_score bits non-zero with
+ * transitions == 5; T == 0 or T > 2^24; frame_stride_bytes < C * the element size unless T == 1, or d_rows or
+ * either stride not a multiple of the element size; codes_row_stride < T unless nrows <= 1; nrows >= 2^32; a
+ * row that exceeds the scratch cap; with nrows > 0 a NULL d_rows or d_codes.  nrows == 0 returns PGN_OK and
+ * touches nothing.  pgn_ctx_set_crf_scratch refuses a NULL ctx.
+ * Not covered: beam search, posteriors and forward-backward; quality strings; bfloat16 scores; a decode that
+ * stops at a short row's valid samples (padding frames are decoded, and the stitch drops them); alphabets
+ * other than 4 bases. */
+#define PGN_CRF_DEFAULT_SCRATCH 1073741824ull
+typedef struct pgn_crf_params {
+    uint32_t state_len;     /* k, 1..5: S = 4^k states */
+    uint32_t transitions;   /* 5 (stay + 4 moves per state) or 4 (moves only, stays score stay_score) */
+    uint32_t score_type;    /* PGN_OUT_F32 or PGN_OUT_F16 */
+    float    stay_score;    /* transitions == 4: the score of every stay; else +0.0f */
+} pgn_crf_params;
+
+int pgn_ctx_set_crf_scratch(pgn_ctx *ctx, uint64_t bytes);
+int pgn_crf_viterbi_rows_device(pgn_ctx *ctx, const pgn_crf_params *params, uint64_t nrows, uint32_t T,
+                                const void *d_rows, uint64_t row_stride_bytes, uint64_t frame_stride_bytes,
+                                uint8_t *d_codes, uint64_t codes_row_stride, float *d_row_score /* may be NULL */,
+                                void *stream);
 
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->

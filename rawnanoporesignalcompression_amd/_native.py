@@ -102,6 +102,16 @@ class CtcParams(C.Structure):
                 ("alphabet", C.c_uint8 * 64)]
 
 
+PGN_CRF_DEFAULT_SCRATCH = 1 << 30  # the cap pgn_ctx_set_crf_scratch(ctx, 0) restores
+PGN_CRF_MAX_FRAMES = 1 << 24
+
+
+class CrfParams(C.Structure):
+    """pgn_crf_params"""
+    _fields_ = [("state_len", C.c_uint32), ("transitions", C.c_uint32), ("score_type", C.c_uint32),
+                ("stay_score", C.c_float)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -174,6 +184,9 @@ SIGNATURES = [
     ("pgn_collapse_codes_device", C.c_int,
      [_VP, C.POINTER(C.c_uint8 * 128), _SZ, _U64P, _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _U64P, _I32P, _U32P,
       _VP]),
+    ("pgn_ctx_set_crf_scratch", C.c_int, [_VP, C.c_uint64]),
+    ("pgn_crf_viterbi_rows_device", C.c_int,
+     [_VP, C.POINTER(CrfParams), C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _VP, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

@@ -29,6 +29,8 @@ the frames doubled where rows overlap and lay each read's frames end to end (:fu
 host).  :meth:`PGNanoCodec.ctc_decode` turns those frames into bases by the best-path CTC rule, and
 :meth:`PGNanoCodec.collapse_codes` is its second half for per-frame codes of any source
 (:func:`ctc_decode_signal` and :func:`collapse_codes_signal` on the host).
+:meth:`PGNanoCodec.crf_viterbi` is the decoder of CRF models: it turns the model's rows into such codes before
+they are stitched (:func:`crf_viterbi_signal` on the host).
 """
 from __future__ import annotations
 
@@ -438,6 +440,74 @@ def ctc_decode_signal(scores, alphabet="NACGT", blank=0):
     codes = (labels | np.where(emit, 0x80, 0)).astype(np.uint8)
     seq, at = collapse_codes_signal(codes, bytes(prm.alphabet))
     return seq, at, scores[at, labels[at]].astype(np.float32), codes
+
+
+@dataclass
+class CrfCodes:
+    """What :meth:`PGNanoCodec.crf_viterbi` leaves on the device."""
+    codes: "object"      # uint8 [N, T]: the newest base of the frame's state, bit 7 set where the path moves
+    row_score: "object"  # float32 [N]: the score of each row's best path; or None
+    params: "object"     # the pgn_crf_params of the call
+
+
+def crf_params(state_len, transitions=5, dtype=np.float16, stay_score=0.0):
+    """``pgn_crf_params``: ``4 ** state_len`` states (``state_len`` in 1..5) with ``transitions`` scores each
+    per frame, of ``dtype`` (float16 or float32): 5 is a stay and four moves, 4 is the four moves with every
+    stay scoring the constant ``stay_score`` (which must be +0.0 with 5)."""
+    k, tr = int(state_len), int(transitions)
+    types = {np.dtype(np.float32): _native.PGN_OUT_F32, np.dtype(np.float16): _native.PGN_OUT_F16}
+    if not 1 <= k <= 5:
+        raise ValueError(f"state_len must lie in 1..5 (got {k})")
+    if tr not in (4, 5):
+        raise ValueError(f"transitions must be 4 or 5 (got {tr})")
+    if np.dtype(dtype) not in types:
+        raise ValueError("scores must be float16 or float32")
+    stay = np.float32(stay_score)
+    if tr == 5 and stay.view(np.uint32) != 0:
+        raise ValueError("stay_score must be +0.0 with transitions == 5 (the stay scores are the model's)")
+    return _native.CrfParams(k, tr, types[np.dtype(dtype)], float(stay))
+
+
+def crf_viterbi_signal(scores, state_len, transitions=5, stay_score=0.0):
+    """The best-path decode of one row's ``[T, C]`` CRF scores on the host (include/pgnano_hip.h, "Model rows to
+    per-frame codes (CRF)"), ``C = transitions * 4 ** state_len``: float32 adds and ``>`` alone, a loop over the
+    frames vectorised over the states.  Returns ``(codes, row_score)``: one uint8 per frame (the newest base of
+    the frame's state, bit 7 set where the path moves into it) and the float32 score of the path.
+    :meth:`PGNanoCodec.crf_viterbi` writes these values for every row."""
+    scores = np.asarray(scores)
+    if scores.ndim != 2:
+        raise ValueError("scores must be [T, C]")
+    prm = crf_params(state_len, transitions, scores.dtype, stay_score)
+    tr, S = prm.transitions, 4 ** prm.state_len
+    T = scores.shape[0]
+    if scores.shape[1] != tr * S or not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
+        raise ValueError(f"scores must be [T, {tr * S}] with 1 <= T <= 2^24 (got {scores.shape})")
+    x = scores.astype(np.float32).reshape(T, S, tr)
+    pred = (np.arange(4)[:, None] * S + np.arange(S)[None, :]) >> 2  # p(s, b) as [b, s]
+    stay = np.float32(prm.stay_score)
+    a = np.zeros(S, np.float32)
+    bp = np.zeros((T, S), np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(T):
+            best = a + (x[t, :, 0] if tr == 5 else stay)
+            for b in range(4):
+                cand = a[pred[b]] + x[t, :, tr - 4 + b]
+                take = cand > best
+                best = np.where(take, cand, best)
+                bp[t, take] = 1 + b
+            a = best
+        e, m = 0, a[0]
+        for s in range(1, S):
+            if a[s] > m:
+                e, m = s, a[s]
+    codes = np.zeros(T, np.uint8)
+    s = e
+    for t in range(T - 1, -1, -1):
+        j = int(bp[t, s])
+        codes[t] = (s & 3) | (0x80 if j else 0)
+        if j:
+            s = ((j - 1) * S + s) >> 2
+    return codes, np.float32(m)
 
 
 @dataclass
@@ -986,6 +1056,69 @@ class PGNanoCodec:
                 _ptr(bases), _ptr(status), _ptr(bf), ls.cuda_stream))
         caller.wait_stream(ls)
         return DecodedReads(seq, bases, status, bf, None, codes, table)
+
+    def set_crf_scratch(self, nbytes: int = 0) -> None:
+        """The cap on the scratch of :meth:`crf_viterbi` (pgn_ctx_set_crf_scratch): the backpointers take
+        ``4 * 4 ** state_len * ceil(T / 8) + 16`` bytes per row, and the rows of a call are decoded in groups that
+        fit the cap.  0 restores the default, 1 GiB.  A call whose single row exceeds the cap is refused."""
+        nbytes = int(nbytes)
+        if not 0 <= nbytes < 1 << 64:
+            raise ValueError("the scratch cap is a uint64")
+        _check(self._lib.pgn_ctx_set_crf_scratch(self._h, nbytes))
+
+    def crf_viterbi(self, rows, state_len, *, transitions=None, stay_score=0.0, time_major: bool = False, codes=None,
+                    row_score: bool = True, stream: int | None = None) -> CrfCodes:
+        """The best-path (Viterbi) decode of a CRF model's rows (pgn_crf_viterbi_rows_device): per row
+        :func:`crf_viterbi_signal` of its scores.
+
+        rows: the model's output for one batch, ``[N, T, C]`` or with ``time_major`` ``[T, N, C]``, float16 or
+        float32, the last dimension contiguous, the other two of any strides (the frame stride at least ``C``);
+        ``C`` is ``5 * 4 ** state_len`` or ``4 * 4 ** state_len``, which decides ``transitions`` when it is
+        None.  codes: a uint8 ``[N, T]`` tensor to write into, its last dimension contiguous and its row stride at
+        least ``T`` (default: a new one).  ``row_score``: whether the rows' path scores are made.  No host wait.
+
+        The codes are the bytes :meth:`collapse_codes` reads, and :meth:`stitch` moves one-byte frames, so for
+        table rows ``[first_segment, first_segment + N)`` of a segmented batch::
+
+            result = codec.crf_viterbi(model(rows), state_len)
+            frames = codec.stitch(plan, result.codes, first_segment, out=frames)
+            bases = codec.collapse_codes(frames, plan.read_frames, "ACGT")
+        """
+        import torch
+
+        _require_device(rows, "rows", self.device)
+        if rows.dim() != 3 or rows.dtype not in (torch.float16, torch.float32):
+            raise ValueError("rows must be a [N, T, C] (or [T, N, C]) tensor of float16 or float32")
+        nd, td = (1, 0) if time_major else (0, 1)
+        N, T, C_ = int(rows.shape[nd]), int(rows.shape[td]), int(rows.shape[2])
+        S = 4 ** int(state_len) if 1 <= int(state_len) <= 5 else 0
+        if transitions is None:
+            transitions = 4 if C_ == 4 * S else 5
+        prm = crf_params(state_len, transitions, np.float16 if rows.dtype == torch.float16 else np.float32, stay_score)
+        if C_ != prm.transitions * S:
+            raise ValueError(f"rows must have {prm.transitions * S} scores per frame (got {C_})")
+        if not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
+            raise ValueError("rows must have between 1 and 2^24 frames")
+        if rows.stride(2) != 1 or (T > 1 and rows.stride(td) < C_) or rows.stride(nd) < 0:
+            raise ValueError("the last dimension of rows must be contiguous and the frame stride at least C")
+        item = rows.element_size()
+        caller = torch.cuda.current_stream()
+        ls = self._launch_stream(stream)
+        with torch.cuda.stream(ls):
+            if codes is None:
+                codes = torch.empty((N, T), dtype=torch.uint8, device=rows.device)
+            else:
+                _require_device(codes, "codes", self.device)
+                if (codes.dtype != torch.uint8 or tuple(codes.shape) != (N, T) or (T > 1 and codes.stride(1) != 1)
+                        or (N > 1 and codes.stride(0) < T)):
+                    raise ValueError(f"codes must be a uint8 [{N}, {T}] tensor, rows contiguous and at least T apart")
+            score = torch.empty(N, dtype=torch.float32, device=rows.device) if row_score else None
+            if N:
+                _check(self._lib.pgn_crf_viterbi_rows_device(
+                    self._h, C.byref(prm), N, T, _ptr(rows), int(rows.stride(nd)) * item, int(rows.stride(td)) * item,
+                    _ptr(codes), max(int(codes.stride(0)), T) if N > 1 else T, _ptr(score), ls.cuda_stream))
+        caller.wait_stream(ls)
+        return CrfCodes(codes, score, prm)
 
     def decompress_reads_norm(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, *,
                               mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0,

@@ -21,6 +21,7 @@
 #include "pgn_segment.h"
 #include "pgn_stitch.h"
 #include "pgn_ctc.h"
+#include "pgn_crf.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2130,6 +2131,12 @@ struct pgn_ctx {
     // and the spans' sums with the total, in one block; the code bytes of a decode whose caller passes no array
     DevBuf<uint64_t> ctcSums{bufs};
     DevBuf<uint8_t> ctcCodes{bufs};
+    // pgn_crf_viterbi_rows_device: the backpointers of one group of rows (crf::row_scratch_bytes each), at most
+    // crfCap bytes (pgn_ctx_set_crf_scratch); PGN_CRF_TRACEBACK=split moves the traceback into a kernel of its own,
+    // =none leaves it out (measurements only: no codes are written)
+    DevBuf<uint32_t> crfBp{bufs};
+    uint64_t crfCap = crf::kDefaultScratch;
+    int crfTrace = 0;  // 0 in the row's workgroup, 1 split, 2 none
     // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
     // first work items and the slots in one block sized by max_split_reads; the per-read counts the one-workgroup kernel reads.
     // Defaults measured by tools/select_split_timing.py (profiles/select_split_timing.log)
@@ -2244,6 +2251,7 @@ static int ctx_init(pgn_ctx* c)
     if (const char* v = getenv("PGN_DEFER_G")) { const long x = atol(v); if (x > 0) c->deferG = (size_t)x; }
     if (const char* v = getenv("PGN_HUF_WIDE_LAST")) { const long x = atol(v); if (x >= 0) c->hufWideLast = (size_t)x; }
     if (const char* v = getenv("PGN_HUF_PRIO_LAST")) c->hufPrioLast = v[0] == '1';
+    if (const char* v = getenv("PGN_CRF_TRACEBACK")) c->crfTrace = strcmp(v, "split") == 0 ? 1 : strcmp(v, "none") == 0 ? 2 : 0;
     if (const char* v = getenv("PGN_DEFER_TAIL_PLAIN")) { const long x = atol(v); if (x >= 0) c->deferTailPlain = (size_t)x; }
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const char* pe = getenv("PGN_PHASE_PROFILE");
@@ -3730,6 +3738,91 @@ extern "C" int pgn_collapse_codes_device(pgn_ctx* c, const uint8_t alphabet[128]
     a.baseFrame = d_base_frame;
     memcpy(a.alphabet, alphabet, sizeof a.alphabet);
     return ctc_run(c, a, false, false, stream);
+}
+
+// ---- model rows to per-frame codes (pgn_crf.h) --------------------------------------------------------
+extern "C" int pgn_ctx_set_crf_scratch(pgn_ctx* c, uint64_t bytes)
+{
+    if (!c) return PGN_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->crfCap = bytes ? bytes : crf::kDefaultScratch;
+    return PGN_OK;
+}
+
+template <uint32_t K, typename E, uint32_t TR>
+static void crf_launch_one(const crf::Args& a, hipStream_t s)
+{
+    hipLaunchKernelGGL((crf::crf_forward_kernel<K, E, TR>), dim3((unsigned)a.nrows), dim3(crf::Shape<K, E, TR>::kThreads), 0,
+                       s, a);
+}
+template <uint32_t K>
+static void crf_launch_k(const crf::Args& a, bool f32, uint32_t tr, hipStream_t s)
+{
+    if (f32)
+        tr == 5 ? crf_launch_one<K, float, 5>(a, s) : crf_launch_one<K, float, 4>(a, s);
+    else
+        tr == 5 ? crf_launch_one<K, _Float16, 5>(a, s) : crf_launch_one<K, _Float16, 4>(a, s);
+}
+
+extern "C" int pgn_crf_viterbi_rows_device(pgn_ctx* c, const pgn_crf_params* params, uint64_t nrows, uint32_t T,
+                                           const void* d_rows, uint64_t row_stride_bytes, uint64_t frame_stride_bytes,
+                                           uint8_t* d_codes, uint64_t codes_row_stride, float* d_row_score, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!crf::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if (T == 0 || T > crf::kMaxT) return PGN_ERR_INVALID_ARG;
+    const uint32_t elem = ctc::elem_bytes(params->score_type), S = crf::states(params->state_len);
+    const uint64_t frameBytes = (uint64_t)params->transitions * S * elem;
+    if (frame_stride_bytes < frameBytes && T != 1) return PGN_ERR_INVALID_ARG;
+    if ((uintptr_t)d_rows % elem || row_stride_bytes % elem || frame_stride_bytes % elem) return PGN_ERR_INVALID_ARG;
+    if (codes_row_stride < T && nrows > 1) return PGN_ERR_INVALID_ARG;
+    if (nrows >> 32) return PGN_ERR_INVALID_ARG;
+    // a missing array is refused behind the scratch cap, with the same status: only the cap needs the context
+    if (nrows && (!d_rows || !d_codes)) return PGN_ERR_INVALID_ARG;
+    const uint64_t rowBytes = crf::row_scratch_bytes(S, T);
+    uint64_t cap;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        cap = c->crfCap;
+    }
+    if (rowBytes > cap) return PGN_ERR_INVALID_ARG;
+    if (nrows == 0) return PGN_OK;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    const uint64_t groupRows = std::min<uint64_t>(cap / rowBytes, 1u << 30);
+    const int rc = reserve(c, {{c->crfBp, (size_t)(std::min(nrows, groupRows) * rowBytes)}});
+    if (rc != PGN_OK) return rc;
+    crf::Args a{};
+    a.rowStride = row_stride_bytes;
+    a.frameStride = frame_stride_bytes;
+    a.T = T;
+    a.split = c->crfTrace ? 1u : 0u;
+    a.stay = params->stay_score;
+    a.codesStride = codes_row_stride;
+    a.bp = c->crfBp;
+    a.rowWords = rowBytes / 4;
+    // the groups follow each other on the stream, so each finds the scratch free
+    for (uint64_t g0 = 0; g0 < nrows; g0 += groupRows) {
+        a.nrows = std::min(groupRows, nrows - g0);
+        a.rows = static_cast<const uint8_t*>(d_rows) + g0 * row_stride_bytes;
+        a.codes = d_codes + g0 * codes_row_stride;
+        a.rowScore = d_row_score ? d_row_score + g0 : nullptr;
+        const bool f32 = params->score_type == PGN_OUT_F32;
+        switch (params->state_len) {
+        case 1: crf_launch_k<1>(a, f32, params->transitions, s); break;
+        case 2: crf_launch_k<2>(a, f32, params->transitions, s); break;
+        case 3: crf_launch_k<3>(a, f32, params->transitions, s); break;
+        case 4: crf_launch_k<4>(a, f32, params->transitions, s); break;
+        default: crf_launch_k<5>(a, f32, params->transitions, s); break;
+        }
+        HIPCHK(hipGetLastError());
+        if (c->crfTrace == 1) {
+            hipLaunchKernelGGL(crf::crf_traceback_kernel, dim3((unsigned)((a.nrows + 63) / 64)), dim3(64), 0, s, a, S);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return PGN_OK;
 }
 
 // ---- in-library entry points of the POD5 loader (pgn_internal.h) --------------------------------
