@@ -31,15 +31,24 @@ host).  :meth:`PGNanoCodec.ctc_decode` turns those frames into bases by the best
 (:func:`ctc_decode_signal` and :func:`collapse_codes_signal` on the host).
 :meth:`PGNanoCodec.crf_viterbi` is the decoder of CRF models: it turns the model's rows into such codes before
 they are stitched (:func:`crf_viterbi_signal` on the host).
+
+The host side of those stages -- every ``*_signal`` model, the ``*_bound`` functions and the ``*_params``
+builders -- lives in :mod:`.host`, which needs NumPy alone.  This module holds the error type, the result
+containers, the codecs and the plugin functions.  Every device call of :class:`PGNanoCodec` runs inside
+:meth:`PGNanoCodec._launch`, where the stream contract is stated, and prepares its arguments with the helpers
+below (:func:`_out_type`, :func:`_to`, :func:`_packed_offsets`, :func:`_reads_layout`, :func:`_require_out`).
 """
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _native
+from .host import (_alphabet_bytes, _trim_struct, crf_params, ctc_params, norm_params, segment_bound, segment_params,
+                   stitch_params)
 
 MAX_CHUNK_SAMPLES = _native.PGN_MAX_CHUNK_SAMPLES
 
@@ -68,23 +77,6 @@ def compressed_signal_max_size(sample_count: int) -> int:
     return int(_native.load().pgn_compressed_signal_max_size(sample_count))
 
 
-def calibrate_signal(adc, offset, scale, dtype=np.float32):
-    """The calibrated signal of int16 ADC counts on the host, ``pA = (adc + offset) * scale`` in float32
-    (the reference reader's ``Read.calibrate_signal_array``, pod5/python/pod5/src/pod5/reader.py:356-368):
-    the int16 converted exactly, one float32 add, one float32 multiply; ``dtype=np.float16`` rounds that
-    value once.  :meth:`PGNanoCodec.decompress_batch_pa` writes these bits from the decode kernels."""
-    pa = (np.asarray(adc, dtype=np.int16).astype(np.float32) + np.float32(offset)) * np.float32(scale)
-    return pa if np.dtype(dtype) == np.float32 else pa.astype(dtype)
-
-
-def normalise_signal(adc, centre, spread, dtype=np.float32):
-    """The normalised signal on the host, ``(adc + (-centre)) * (1 / spread)`` in float32: the int16
-    converted exactly, one float32 division for the reciprocal, one add, one multiply;
-    ``dtype=np.float16`` rounds that value once.  :meth:`PGNanoCodec.decompress_reads_norm` writes these bits."""
-    inv = np.float32(1.0) / np.float32(spread)
-    return calibrate_signal(adc, -np.float32(centre), inv, dtype)
-
-
 def _ptr(t) -> int:
     return t.data_ptr() if t is not None else 0
 
@@ -95,47 +87,96 @@ def _require_device(t, name: str, device: int) -> None:
         raise ValueError(f"{name} must be a tensor on cuda:{device} (got {t.device})")
 
 
-class ReadStats:
-    """``pgn_read_stats`` of every read as named columns over one device tensor (``raw``: uint8,
-    nreads x 32, the C struct's bytes).  ``n`` int64, ``status`` int32, ``q_lo`` / ``q_hi`` int16, ``m2``
-    int32, ``mad4`` int32 (the uint32's bits; it stays below 2^18), ``centre`` / ``spread`` float32:
-    views, no copies.  :meth:`numpy` gives the same as a structured host array."""
-
-    DTYPE = np.dtype([("n", "<u8"), ("status", "<i4"), ("q_lo", "<i2"), ("q_hi", "<i2"), ("m2", "<i4"),
-                      ("mad4", "<u4"), ("centre", "<f4"), ("spread", "<f4")])
-    _COLS = {"n": ("int64", 0), "status": ("int32", 2), "q_lo": ("int16", 6), "q_hi": ("int16", 7), "m2": ("int32", 4),
-             "mad4": ("int32", 5), "centre": ("float32", 6), "spread": ("float32", 7)}
-
-    def __init__(self, raw):
-        self.raw = raw
-
-    def __len__(self):
-        return int(self.raw.shape[0])
-
-    def __getattr__(self, name):
-        import torch
-
-        if name in ReadStats._COLS:
-            t, col = ReadStats._COLS[name]
-            return self.raw.view(getattr(torch, t))[:, col]
-        raise AttributeError(name)
-
-    def numpy(self):
-        return self.raw.cpu().numpy().reshape(-1).view(ReadStats.DTYPE)
+def _require_out(t, name: str, device: int, dtype=None) -> None:
+    """A destination or workspace the caller may pass: on the device and, where one is asked, of ``dtype``."""
+    if t is not None:
+        _require_device(t, name, device)
+        if dtype is not None and t.dtype != dtype:
+            raise ValueError(f"{name} must have dtype {dtype} (got {t.dtype})")
 
 
-def norm_params(mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0):
-    """``pgn_norm_params`` from Python values (the defaults live here; the C ABI has none)."""
-    if mode not in _native.NORM_MODES:
-        raise ValueError(f"mode must be one of {sorted(_native.NORM_MODES)} (got {mode!r})")
-    return _native.NormParams(_native.NORM_MODES[mode], 0, float(p[0]), float(p[1]), float(centre_mult),
-                              float(spread_mult), float(spread_floor), 0.0)
+def _nreads(read_first_chunk) -> int:
+    n = int(read_first_chunk.numel()) - 1
+    if n < 0:
+        raise ValueError("read_first_chunk needs nreads + 1 entries")
+    return n
+
+
+def _out_type(dtype, int16: bool = False) -> int:
+    """The ``PGN_OUT_*`` value of a torch dtype: float32 or float16, and int16 where a call writes samples too."""
+    import torch
+
+    types = {torch.float32: _native.PGN_OUT_F32, torch.float16: _native.PGN_OUT_F16}
+    if int16:
+        types[torch.int16] = _native.PGN_OUT_INT16
+    if dtype not in types:
+        names = "torch.float32, torch.float16 or torch.int16" if int16 else "torch.float32 or torch.float16"
+        raise ValueError(f"dtype must be {names} (got {dtype})")
+    return types[dtype]
+
+
+def _to(t, dev, dtype):
+    """An argument as the kernels read it: on ``dev``, of ``dtype``, contiguous; None stays None."""
+    return None if t is None else t.to(device=dev, dtype=dtype).contiguous()
+
+
+def _packed_offsets(n: int, sizes):
+    """Where each of ``n`` chunks starts when they lie end to end: the sum of the ``sizes`` (counts or
+    capacities) before it, int64."""
+    import torch
+
+    offs = torch.zeros(n, dtype=torch.int64, device=sizes.device)
+    if n > 1:
+        offs[1:] = torch.cumsum(sizes.to(torch.int64), 0)[:-1]
+    return offs
+
+
+def _reads_layout(counts, first, read_out_offsets):
+    """``(ends, read_out_offsets)`` of chunks in read order: ``ends[i]`` is the samples before chunk ``i``
+    (chunks + 1 entries), and a read whose offset is not given starts where its first chunk would."""
+    import torch
+
+    ends = torch.zeros(int(counts.numel()) + 1, dtype=torch.int64, device=counts.device)
+    ends[1:] = torch.cumsum(counts.to(torch.int64), 0)
+    if read_out_offsets is None:
+        return ends, ends[first[:-1]].contiguous()
+    return ends, _to(read_out_offsets, counts.device, torch.int64)
+
+
+def _chunk_arrays(blobs, blob_offsets, blob_sizes, sample_counts, out, out_offsets, dtype):
+    """What both chunk decodes read, made on the launch stream: ``(counts, out_offsets, out, blob_offsets,
+    blob_sizes)``.  Offsets that are not given are packed; an ``out`` that is not given is allocated for the sum of
+    the counts, which waits for it on the host."""
+    import torch
+
+    dev = blobs.device
+    counts = _to(sample_counts, dev, torch.int32)
+    so = _packed_offsets(int(counts.numel()), counts) if out_offsets is None else _to(out_offsets, dev, torch.int64)
+    if out is None:
+        total = int(counts.to(torch.int64).sum().item())
+        out = torch.empty(max(total, 1), dtype=dtype, device=dev)
+    return counts, so, out, _to(blob_offsets, dev, torch.int64), _to(blob_sizes, dev, torch.int64)
+
+
+def _read_arrays(blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, out, read_out_offsets, dtype):
+    """What both reads decodes read, made on the launch stream: ``(counts, read_first_chunk, read_out_offsets,
+    out, blob_offsets, blob_sizes)``.  Read offsets that are not given are packed; an ``out`` that is not given
+    is allocated for the sum of the counts, which waits for it on the host."""
+    import torch
+
+    dev = blobs.device
+    counts = _to(sample_counts, dev, torch.int32)
+    first = _to(read_first_chunk, dev, torch.int64)
+    ends, ro = _reads_layout(counts, first, read_out_offsets)
+    if out is None:
+        out = torch.empty(max(int(ends[-1].item()), 1), dtype=dtype, device=dev)
+    return counts, first, ro, out, _to(blob_offsets, dev, torch.int64), _to(blob_sizes, dev, torch.int64)
 
 
 class _Columns:
-    """Named column views over one device tensor of C structs (``raw``: uint8, records x struct bytes), as
-    :class:`ReadStats` has them: views, no copies; unsigned 32-bit fields come as int32 (their bits).
-    :meth:`numpy` gives the same as a structured host array."""
+    """Named column views over one device tensor of C structs (``raw``: uint8, records x struct bytes): views,
+    no copies; unsigned 32-bit fields come as int32 (their bits).  :meth:`numpy` gives the same as a structured
+    host array."""
 
     DTYPE = None
     _COLS = {}
@@ -157,6 +198,17 @@ class _Columns:
 
     def numpy(self):
         return self.raw.cpu().numpy().reshape(-1).view(type(self).DTYPE)
+
+
+class ReadStats(_Columns):
+    """``pgn_read_stats`` of every read (``raw``: nreads x 32).  ``n`` int64, ``status`` int32, ``q_lo`` /
+    ``q_hi`` int16, ``m2`` int32, ``mad4`` int32 (the uint32's bits; it stays below 2^18), ``centre`` /
+    ``spread`` float32."""
+
+    DTYPE = np.dtype([("n", "<u8"), ("status", "<i4"), ("q_lo", "<i2"), ("q_hi", "<i2"), ("m2", "<i4"),
+                      ("mad4", "<u4"), ("centre", "<f4"), ("spread", "<f4")])
+    _COLS = {"n": ("int64", 0), "status": ("int32", 2), "q_lo": ("int16", 6), "q_hi": ("int16", 7), "m2": ("int32", 4),
+             "mad4": ("int32", 5), "centre": ("float32", 6), "spread": ("float32", 7)}
 
 
 class ReadSegments(_Columns):
@@ -186,133 +238,6 @@ class SegmentedReads:
     total: "object"     # int64 device scalar: the segments the batch needs
 
 
-def trim_params(max_samples=8000, window=40, min_elements=3, min_trim=10, mad_mult=1.4826, threshold_mads=2.4):
-    """``pgn_trim_params`` from Python values (the usual values live here; the C ABI has none).
-    ``max_samples=0`` turns trimming off."""
-    return _native.TrimParams(int(max_samples), int(window), int(min_elements), int(min_trim), float(mad_mult),
-                              float(threshold_mads))
-
-
-def _trim_struct(trim):
-    """None / False: trimming off; True: the usual values; a dict: :func:`trim_params` of it; or the struct."""
-    if trim is None or trim is False:
-        return trim_params(max_samples=0)
-    if trim is True:
-        return trim_params()
-    if isinstance(trim, _native.TrimParams):
-        return trim
-    return trim_params(**trim)
-
-
-def segment_params(length, overlap):
-    """``pgn_segment_params``: rows of ``length`` elements, neighbours sharing ``overlap`` of them."""
-    length, overlap = int(length), int(overlap)
-    if not (1 <= length <= 1 << 24 and 0 <= overlap < length):
-        raise ValueError(f"need 1 <= length <= 2^24 and 0 <= overlap < length (got {length}, {overlap})")
-    return _native.SegmentParams(length, overlap)
-
-
-def _segment_starts(m: int, length: int, overlap: int):
-    """[(start, valid)] of a trimmed read of m samples (include/pgnano_hip.h, "Segments")."""
-    stride = length - overlap
-    if m == 0:
-        return []
-    if m <= length:
-        return [(0, m)]
-    k = -(-(m - length) // stride) + 1
-    return [(min(j * stride, m - length), length) for j in range(k)]
-
-
-def segment_bound(counts, length, overlap) -> int:
-    """The segments a batch of reads of these (untrimmed) lengths can need: trimming only shortens a read
-    and the count does not decrease with the length, so this is an upper bound, computed on the host."""
-    p = segment_params(length, overlap)
-    n = np.asarray(counts).astype(np.int64).reshape(-1)
-    stride = p.length - p.overlap
-    k = np.where(n > p.length, (np.maximum(n - p.length, 0) + stride - 1) // stride + 1, (n > 0).astype(np.int64))
-    return int(k.sum())
-
-
-def trim_signal(adc, **trim) -> int:
-    """The head trim of one read on the host (include/pgnano_hip.h, "Trim"): the samples to drop.
-    ``**trim`` as in :func:`trim_params`."""
-    T = trim_params(**trim)
-    x = np.asarray(adc, dtype=np.int16).reshape(-1)
-    n = x.size
-    if T.max_samples == 0:
-        return 0
-    H = min(n, T.max_samples)
-    if H < T.min_trim + T.window:
-        return min(T.min_trim, n)
-    v = x[:H].astype(np.int64)
-    s = np.sort(v)
-    m2 = int(s[(H - 1) // 2] + s[H // 2])
-    t = np.sort(np.abs(2 * v - m2))
-    mad4 = int(t[(H - 1) // 2] + t[H // 2])
-    f32 = np.float32
-    thr = f32(0.5) * f32(m2) + f32(T.threshold_mads) * (f32(T.mad_mult) * (f32(0.25) * f32(mad4)))
-    above = x[:H].astype(np.float32) > thr
-    seen = False
-    for w in range((H - T.min_trim) // T.window):
-        e = T.min_trim + (w + 1) * T.window
-        seen = seen or int(above[e - T.window:e].sum()) > T.min_elements
-        if seen and not above[e - 1]:
-            return e if e < H else T.min_trim
-    return T.min_trim
-
-
-def select_parts(n: int, split_min_samples: int, part_samples: int):
-    """The plan of one read's selection on the host (include/pgnano_hip.h, "Long reads"): the boundaries of
-    the parts a read of ``n`` samples is selected in under :meth:`PGNanoCodec.set_select_split`'s settings, as
-    ``parts + 1`` ascending uint64 values from 0 to ``n``.  A read that is not split has one part."""
-    n, split_min_samples, part_samples = int(n), int(split_min_samples), int(part_samples)
-    if not (1024 <= part_samples <= 1 << 24 and part_samples <= split_min_samples < 1 << 32) or n < 0:
-        raise ValueError("need 1024 <= part_samples <= 2**24 and part_samples <= split_min_samples < 2**32")
-    parts = 1
-    if split_min_samples < n < 1 << 32:
-        parts = min(-(-n // part_samples), _native.PGN_SELECT_MAX_PARTS)
-    return np.array([j * n // parts for j in range(parts + 1)], dtype=np.uint64)
-
-
-def _host_stats(y, prm):
-    """(centre, spread) of one read on the host, as the per-read normalisation section defines them."""
-    f32 = np.float32
-    s = np.sort(y.astype(np.int64))
-    n = s.size
-    if prm.mode == _native.PGN_NORM_QUANTILE:
-        a = int(s[int(np.floor(np.float64(prm.p_lo) * np.float64(n - 1)))])
-        b = int(s[int(np.floor(np.float64(prm.p_hi) * np.float64(n - 1)))])
-        centre, spread = f32(prm.centre_mult) * f32(a + b), f32(prm.spread_mult) * f32(b - a)
-    else:
-        m2 = int(s[(n - 1) // 2] + s[n // 2])
-        t = np.sort(np.abs(2 * y.astype(np.int64) - m2))
-        centre = f32(0.5) * f32(m2)
-        spread = f32(prm.spread_mult) * (f32(0.25) * f32(int(t[(n - 1) // 2] + t[n // 2])))
-    return centre, max(spread, f32(prm.spread_floor))
-
-
-def segment_signal(adc, length, overlap, trim=None, dtype=np.float16, **norm):
-    """The model segments of one read on the host, ``[segments, length]``: the read without its trimmed head
-    (``trim`` as in :meth:`PGNanoCodec.segment_reads`), normalised by its own statistics (``**norm`` as in
-    :func:`norm_params`; :func:`normalise_signal`'s arithmetic), cut into rows that overlap by ``overlap``, the
-    last aligned to the read's end, a short read padded with +0.0.  :meth:`PGNanoCodec.segment_reads` writes
-    these bits."""
-    p = segment_params(length, overlap)
-    prm = norm_params(**norm)
-    T = _trim_struct(trim)
-    x = np.asarray(adc, dtype=np.int16).reshape(-1)
-    y = x[trim_signal(x, **{f: getattr(T, f) for f, _ in T._fields_}):]
-    plan = _segment_starts(y.size, p.length, p.overlap)
-    rows = np.zeros((len(plan), p.length), dtype)
-    if plan:
-        centre, spread = _host_stats(y, prm)
-        with np.errstate(over="ignore"):  # binary16 overflow is +-inf, as on the device
-            z = normalise_signal(y, centre, spread, dtype)
-        for j, (start, valid) in enumerate(plan):
-            rows[j, :valid] = z[start:start + valid]
-    return rows
-
-
 class StitchTable(_Columns):
     """``pgn_stitch_segment`` of every segment: frames ``[first, first + count)`` of the row are kept and go to
     frame ``dst_frame`` (int64) on; ``first`` and ``count`` int32."""
@@ -327,45 +252,6 @@ class StitchPlan:
     segments: StitchTable   # one entry per row of the segment table it was made from
     read_frames: "object"   # int64, reads + 1: read r's frames are [read_frames[r], read_frames[r + 1])
     params: "object"        # the pgn_stitch_params it was made with
-
-
-def stitch_params(length, overlap, frame_samples):
-    """``pgn_stitch_params``: the ``length`` and ``overlap`` the segments were cut with and the model's stride
-    ``frame_samples``, which divides ``length`` and does not exceed ``length - overlap``."""
-    L, V, s = int(length), int(overlap), int(frame_samples)
-    if not (1 <= s and 1 <= L <= 1 << 24 and L % s == 0 and 0 <= V and s <= L - V):
-        raise ValueError("need 1 <= frame_samples, length % frame_samples == 0, 0 <= overlap, frame_samples <= "
-                         f"length - overlap and length <= 2^24 (got {L}, {V}, {s})")
-    return _native.StitchParams(L, V, s, 0)
-
-
-def stitch_plan_signal(m_or_segments, length, overlap, frame_samples):
-    """The kept frames of one read's segments on the host (include/pgnano_hip.h, "Model output back to
-    reads"): ``[segments, 2]`` int64, ``first`` and ``count`` per segment.  ``m_or_segments`` is the trimmed
-    read's length, or its segments as ``(start, valid)`` rows of the segment table (any common origin of the
-    starts).  :meth:`PGNanoCodec.stitch_plan` writes these values for a read that is taken."""
-    p = stitch_params(length, overlap, frame_samples)
-    L, s, T = p.length, p.frame_samples, p.length // p.frame_samples
-    segs = _segment_starts(int(m_or_segments), L, p.overlap) if np.isscalar(m_or_segments) else m_or_segments
-    segs = np.asarray(segs, dtype=np.int64).reshape(-1, 2)
-    k = segs.shape[0]
-    if k == 0:
-        return np.zeros((0, 2), np.int64)
-    a, valid = segs[:, 0] - segs[0, 0], segs[:, 1]
-    half = (a[:-1] + L - a[1:]) // 2           # half the overlap of segments j and j + 1, rounded down
-    lo = np.concatenate([[0], half])           # c_{j-1} - a_j
-    hi = np.concatenate([a[1:] - a[:-1] + half, valid[-1:]])  # c_j - a_j
-    first = np.minimum(-(-lo // s), T)
-    end = np.minimum(-(-hi // s), T)
-    return np.stack([first, np.maximum(end - first, 0)], 1)
-
-
-def stitch_bound(counts, length, overlap, frame_samples) -> int:
-    """The frames a batch of reads of these (untrimmed) lengths can give: ``ceil(n / s) + segments(n)`` per
-    read bounds the frames of every trimmed length, so this is an upper bound computed on the host."""
-    p = stitch_params(length, overlap, frame_samples)
-    n = np.asarray(counts).astype(np.int64).reshape(-1)
-    return int((-(-n // p.frame_samples)).sum()) + segment_bound(n, p.length, p.overlap)
 
 
 @dataclass
@@ -387,127 +273,12 @@ class DecodedReads:
         return [seq[a:b].tobytes() for a, b in zip(rb[:-1], rb[1:])]
 
 
-def _alphabet_bytes(alphabet, entries):
-    a = alphabet.encode("latin-1") if isinstance(alphabet, str) else bytes(bytearray(alphabet))
-    if len(a) > entries:
-        raise ValueError(f"alphabet has {len(a)} entries, at most {entries} fit")
-    return a
-
-
-def ctc_params(classes, blank=0, alphabet="NACGT", dtype=np.float16):
-    """``pgn_ctc_params``: ``classes`` scores per frame (2..64) of ``dtype`` (float16 or float32), class
-    ``blank`` emits nothing, class ``c`` writes ``alphabet[c]`` (one byte per class)."""
-    C_, blank = int(classes), int(blank)
-    a = _alphabet_bytes(alphabet, 64)
-    types = {np.dtype(np.float32): _native.PGN_OUT_F32, np.dtype(np.float16): _native.PGN_OUT_F16}
-    if not (2 <= C_ <= 64 and 0 <= blank < C_):
-        raise ValueError(f"need 2 <= classes <= 64 and 0 <= blank < classes (got {C_}, {blank})")
-    if len(a) != C_:
-        raise ValueError(f"alphabet must have one entry per class ({C_}), got {len(a)}")
-    if np.dtype(dtype) not in types:
-        raise ValueError("scores must be float16 or float32")
-    return _native.CtcParams(C_, blank, types[np.dtype(dtype)], 0, (C.c_uint8 * 64)(*a))
-
-
-def collapse_codes_signal(codes, alphabet):
-    """The bases of one read's code bytes on the host (include/pgnano_hip.h, "Stitched frames to bases"): a
-    frame emits iff bit 7 of its code is set, and its base is ``alphabet[code & 0x7f]``.  Returns ``(seq,
-    base_frame)``: uint8 bases and the uint32 frame of each."""
-    codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
-    table = np.zeros(128, np.uint8)
-    a = _alphabet_bytes(alphabet, 128)
-    table[:len(a)] = np.frombuffer(a, np.uint8)
-    at = np.flatnonzero(codes & 0x80)
-    return table[codes[at] & 0x7F], at.astype(np.uint32)
-
-
-def ctc_decode_signal(scores, alphabet="NACGT", blank=0):
-    """The best-path CTC decode of one read's ``[frames, classes]`` scores on the host (include/pgnano_hip.h,
-    "Stitched frames to bases"): the label of a frame is ``np.argmax`` of its scores, a frame emits iff its
-    label is not ``blank`` and it is the read's first frame or its label differs from the frame before.
-    Returns ``(seq, base_frame, base_score, codes)``: uint8 bases, the uint32 frame and the float32 winning
-    score of each, and one code byte per frame (the label, bit 7 set where the frame emits).
-    :meth:`PGNanoCodec.ctc_decode` writes these values for a read that is taken."""
-    scores = np.asarray(scores)
-    if scores.ndim != 2:
-        raise ValueError("scores must be [frames, classes]")
-    prm = ctc_params(scores.shape[1], blank, alphabet, scores.dtype)
-    if scores.shape[0] == 0:
-        return np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, np.uint8)
-    labels = np.argmax(scores, axis=1)
-    emit = labels != prm.blank
-    emit[1:] &= labels[1:] != labels[:-1]
-    codes = (labels | np.where(emit, 0x80, 0)).astype(np.uint8)
-    seq, at = collapse_codes_signal(codes, bytes(prm.alphabet))
-    return seq, at, scores[at, labels[at]].astype(np.float32), codes
-
-
 @dataclass
 class CrfCodes:
     """What :meth:`PGNanoCodec.crf_viterbi` leaves on the device."""
     codes: "object"      # uint8 [N, T]: the newest base of the frame's state, bit 7 set where the path moves
     row_score: "object"  # float32 [N]: the score of each row's best path; or None
     params: "object"     # the pgn_crf_params of the call
-
-
-def crf_params(state_len, transitions=5, dtype=np.float16, stay_score=0.0):
-    """``pgn_crf_params``: ``4 ** state_len`` states (``state_len`` in 1..5) with ``transitions`` scores each
-    per frame, of ``dtype`` (float16 or float32): 5 is a stay and four moves, 4 is the four moves with every
-    stay scoring the constant ``stay_score`` (which must be +0.0 with 5)."""
-    k, tr = int(state_len), int(transitions)
-    types = {np.dtype(np.float32): _native.PGN_OUT_F32, np.dtype(np.float16): _native.PGN_OUT_F16}
-    if not 1 <= k <= 5:
-        raise ValueError(f"state_len must lie in 1..5 (got {k})")
-    if tr not in (4, 5):
-        raise ValueError(f"transitions must be 4 or 5 (got {tr})")
-    if np.dtype(dtype) not in types:
-        raise ValueError("scores must be float16 or float32")
-    stay = np.float32(stay_score)
-    if tr == 5 and stay.view(np.uint32) != 0:
-        raise ValueError("stay_score must be +0.0 with transitions == 5 (the stay scores are the model's)")
-    return _native.CrfParams(k, tr, types[np.dtype(dtype)], float(stay))
-
-
-def crf_viterbi_signal(scores, state_len, transitions=5, stay_score=0.0):
-    """The best-path decode of one row's ``[T, C]`` CRF scores on the host (include/pgnano_hip.h, "Model rows to
-    per-frame codes (CRF)"), ``C = transitions * 4 ** state_len``: float32 adds and ``>`` alone, a loop over the
-    frames vectorised over the states.  Returns ``(codes, row_score)``: one uint8 per frame (the newest base of
-    the frame's state, bit 7 set where the path moves into it) and the float32 score of the path.
-    :meth:`PGNanoCodec.crf_viterbi` writes these values for every row."""
-    scores = np.asarray(scores)
-    if scores.ndim != 2:
-        raise ValueError("scores must be [T, C]")
-    prm = crf_params(state_len, transitions, scores.dtype, stay_score)
-    tr, S = prm.transitions, 4 ** prm.state_len
-    T = scores.shape[0]
-    if scores.shape[1] != tr * S or not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
-        raise ValueError(f"scores must be [T, {tr * S}] with 1 <= T <= 2^24 (got {scores.shape})")
-    x = scores.astype(np.float32).reshape(T, S, tr)
-    pred = (np.arange(4)[:, None] * S + np.arange(S)[None, :]) >> 2  # p(s, b) as [b, s]
-    stay = np.float32(prm.stay_score)
-    a = np.zeros(S, np.float32)
-    bp = np.zeros((T, S), np.uint8)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for t in range(T):
-            best = a + (x[t, :, 0] if tr == 5 else stay)
-            for b in range(4):
-                cand = a[pred[b]] + x[t, :, tr - 4 + b]
-                take = cand > best
-                best = np.where(take, cand, best)
-                bp[t, take] = 1 + b
-            a = best
-        e, m = 0, a[0]
-        for s in range(1, S):
-            if a[s] > m:
-                e, m = s, a[s]
-    codes = np.zeros(T, np.uint8)
-    s = e
-    for t in range(T - 1, -1, -1):
-        j = int(bp[t, s])
-        codes[t] = (s & 3) | (0x80 if j else 0)
-        if j:
-            s = ((j - 1) * S + s) >> 2
-    return codes, np.float32(m)
 
 
 @dataclass
@@ -577,17 +348,22 @@ class PGNanoCodec:
             raise ValueError("max_chunk_samples: the bounded batch calls are C5's")
         return getattr(self._lib, fn)(self._h, bound, *args)
 
-    def _launch_stream(self, stream):
-        """The HIP stream a batch call runs on (the caller's, else the context's), made to wait for
-        the caller's current stream.  The call's own allocations and fills are issued on it too, so
-        they are ordered before the kernels and the caching allocator ties them to that stream.  The
-        batch calls end by making the caller's current stream wait for it (an event, no host sync), so
-        the outputs are usable there like the results of any torch op."""
+    @contextmanager
+    def _launch(self, stream):
+        """The scope every device call runs in; yields the HIP stream the call runs on (the caller's ``stream``,
+        else the context's), made to wait for the caller's current stream.  The body runs with it as torch's
+        current stream: the call's own allocations and fills are issued on it too, so they are ordered before
+        the kernels and the caching allocator ties them to that stream.  On a normal exit the caller's current
+        stream is made to wait for it (an event, no host sync), so the outputs are usable there like the results
+        of any torch op.  An exception leaves without that wait: there are no outputs."""
         import torch
 
-        s = torch.cuda.ExternalStream(int(stream) if stream else self.stream, device=torch.device("cuda", self.device))
-        s.wait_stream(torch.cuda.current_stream())
-        return s
+        caller = torch.cuda.current_stream()
+        ls = torch.cuda.ExternalStream(int(stream) if stream else self.stream, device=torch.device("cuda", self.device))
+        ls.wait_stream(caller)
+        with torch.cuda.stream(ls):
+            yield ls
+        caller.wait_stream(ls)
 
     @property
     def stream(self) -> int:
@@ -658,25 +434,14 @@ class PGNanoCodec:
         import torch
 
         _require_device(samples, "samples", self.device)
-        if out is not None:
-            _require_device(out, "out", self.device)
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        _require_out(out, "out", self.device)
+        with self._launch(stream) as ls:
             dev = samples.device
             n = int(sample_counts.numel())
-            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
-            offs = sample_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            if out_caps is None:
-                caps = self._default_caps(counts)
-            else:
-                caps = out_caps.to(device=dev, dtype=torch.int64).contiguous()
-            if out_offsets is None:
-                oo = torch.zeros(n, dtype=torch.int64, device=dev)
-                if n > 1:
-                    oo[1:] = torch.cumsum(caps, 0)[:-1]
-            else:
-                oo = out_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            counts = _to(sample_counts, dev, torch.int32)
+            offs = _to(sample_offsets, dev, torch.int64)
+            caps = self._default_caps(counts) if out_caps is None else _to(out_caps, dev, torch.int64)
+            oo = _packed_offsets(n, caps) if out_offsets is None else _to(out_offsets, dev, torch.int64)
             if out is None:
                 total = int((oo[-1] + caps[-1]).item()) if n else 0
                 out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
@@ -689,7 +454,6 @@ class PGNanoCodec:
                 _check(self._bounded("pgn_compress_batch_device_bounded", int(max_chunk_samples), *args))
             else:
                 _check(self._call(self._fn_compress_batch, *args))
-        caller.wait_stream(ls)
         return EncodedBatch(out, oo, caps, sizes, status, stats)
 
     def decompress_batch(self, blobs, blob_offsets, blob_sizes, sample_counts, out=None, out_offsets=None,
@@ -699,32 +463,17 @@ class PGNanoCodec:
         import torch
 
         _require_device(blobs, "blobs", self.device)
-        if out is not None:
-            _require_device(out, "out", self.device)
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
-            dev = blobs.device
-            n = int(sample_counts.numel())
-            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
-            if out_offsets is None:
-                so = torch.zeros(n, dtype=torch.int64, device=dev)
-                if n > 1:
-                    so[1:] = torch.cumsum(counts.to(torch.int64), 0)[:-1]
-            else:
-                so = out_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            if out is None:
-                total = int(counts.to(torch.int64).sum().item())
-                out = torch.empty(max(total, 1), dtype=torch.int16, device=dev)
-            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
-            status = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        _require_out(out, "out", self.device)
+        n = int(sample_counts.numel())
+        with self._launch(stream) as ls:
+            counts, so, out, bo, bs = _chunk_arrays(blobs, blob_offsets, blob_sizes, sample_counts, out, out_offsets,
+                                                    torch.int16)
+            status = torch.full((n,), -1, dtype=torch.int32, device=blobs.device)
             args = (n, _ptr(blobs), _ptr(bo), _ptr(bs), _ptr(out), _ptr(so), _ptr(counts), _ptr(status), ls.cuda_stream)
             if max_chunk_samples is not None:
                 _check(self._bounded("pgn_decompress_batch_device_bounded", int(max_chunk_samples), *args))
             else:
                 _check(self._call(self._fn_decompress_batch, *args))
-        caller.wait_stream(ls)
         return out, so, status
 
     @property
@@ -756,46 +505,26 @@ class PGNanoCodec:
         import torch
 
         dtype = torch.float32 if dtype is None else dtype
-        types = {torch.int16: _native.PGN_OUT_INT16, torch.float32: _native.PGN_OUT_F32,
-                 torch.float16: _native.PGN_OUT_F16}
-        if dtype not in types:
-            raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.int16 (got {dtype})")
+        out_type = _out_type(dtype, int16=True)
         if max_chunk_samples is not None and int(max_chunk_samples) <= 0:
             raise ValueError("max_chunk_samples must be > 0 when given (None: no bound)")
         _require_device(blobs, "blobs", self.device)
         n = int(sample_counts.numel())
-        if out is not None:
-            _require_device(out, "out", self.device)
-            if out.dtype != dtype:
-                raise ValueError(f"out must have dtype {dtype} (got {out.dtype})")
+        _require_out(out, "out", self.device, dtype)
         calibrated = dtype != torch.int16
         if calibrated:
             for t, name in ((cal_offset, "cal_offset"), (cal_scale, "cal_scale")):
                 if t is None or int(t.numel()) != n:
                     raise ValueError(f"{name} must have one entry per chunk ({n})")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             dev = blobs.device
-            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
-            if out_offsets is None:
-                so = torch.zeros(n, dtype=torch.int64, device=dev)
-                if n > 1:
-                    so[1:] = torch.cumsum(counts.to(torch.int64), 0)[:-1]
-            else:
-                so = out_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            if out is None:
-                total = int(counts.to(torch.int64).sum().item())
-                out = torch.empty(max(total, 1), dtype=dtype, device=dev)
-            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
-            co = cal_offset.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
-            cs = cal_scale.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
+            counts, so, out, bo, bs = _chunk_arrays(blobs, blob_offsets, blob_sizes, sample_counts, out, out_offsets, dtype)
+            co = _to(cal_offset if calibrated else None, dev, torch.float32)
+            cs = _to(cal_scale if calibrated else None, dev, torch.float32)
             status = torch.full((n,), -1, dtype=torch.int32, device=dev)
             _check(self._lib.pgn_decompress_batch_device_pa(
                 self._h, self._pa_codec, int(max_chunk_samples or 0), n, _ptr(blobs), _ptr(bo), _ptr(bs), _ptr(out),
-                types[dtype], _ptr(so), _ptr(counts), _ptr(co), _ptr(cs), _ptr(status), ls.cuda_stream))
-        caller.wait_stream(ls)
+                out_type, _ptr(so), _ptr(counts), _ptr(co), _ptr(cs), _ptr(status), ls.cuda_stream))
         return out, so, status
 
     def read_stats(self, samples, read_offsets, read_counts, stream: int | None = None, **params) -> ReadStats:
@@ -810,17 +539,13 @@ class PGNanoCodec:
         _require_device(samples, "samples", self.device)
         if samples.dtype != torch.int16:
             raise ValueError(f"samples must be int16 (got {samples.dtype})")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             dev = samples.device
             n = int(read_counts.numel())
-            ro = read_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            rc = read_counts.to(device=dev, dtype=torch.int64).contiguous()
+            ro, rc = _to(read_offsets, dev, torch.int64), _to(read_counts, dev, torch.int64)
             raw = torch.zeros((n, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
             _check(self._lib.pgn_read_stats_device(self._h, n, _ptr(samples), _ptr(ro), _ptr(rc), C.byref(prm),
                                                    _ptr(raw), ls.cuda_stream))
-        caller.wait_stream(ls)
         return ReadStats(raw)
 
     def segment_reads(self, samples, read_offsets, read_counts, *, length, overlap, trim=None, dtype=None,
@@ -843,9 +568,7 @@ class PGNanoCodec:
         import torch
 
         dtype = torch.float16 if dtype is None else dtype
-        types = {torch.float32: _native.PGN_OUT_F32, torch.float16: _native.PGN_OUT_F16}
-        if dtype not in types:
-            raise ValueError(f"dtype must be torch.float32 or torch.float16 (got {dtype})")
+        out_type = _out_type(dtype)
         seg, prm, tprm = segment_params(length, overlap), norm_params(**norm), _trim_struct(trim)
         _require_device(samples, "samples", self.device)
         if samples.dtype != torch.int16:
@@ -866,20 +589,16 @@ class PGNanoCodec:
 
         def i64(a):
             t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a).astype(np.int64))
-            return t.to(device=dev, dtype=torch.int64).contiguous()
+            return _to(t, dev, torch.int64)
 
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             ro, rc = i64(read_offsets), i64(read_counts)
             n = int(rc.numel())
             if int(ro.numel()) != n:
                 raise ValueError("read_offsets and read_counts must have one entry per read")
-            st_in = None
-            if read_status is not None:
-                st_in = read_status.to(device=dev, dtype=torch.int32).contiguous()
-                if int(st_in.numel()) != n:
-                    raise ValueError(f"read_status must have one entry per read ({n})")
+            st_in = _to(read_status, dev, torch.int32)
+            if st_in is not None and int(st_in.numel()) != n:
+                raise ValueError(f"read_status must have one entry per read ({n})")
             if out is None:
                 out = torch.empty((capacity, seg.length), dtype=dtype, device=dev)
             segs = torch.zeros((capacity, C.sizeof(_native.Segment)), dtype=torch.uint8, device=dev)
@@ -888,8 +607,7 @@ class PGNanoCodec:
             total = torch.zeros((), dtype=torch.int64, device=dev)
             _check(self._lib.pgn_segment_reads_device(
                 self._h, n, _ptr(samples), _ptr(ro), _ptr(rc), _ptr(st_in), C.byref(tprm), C.byref(prm), C.byref(seg),
-                _ptr(out), types[dtype], capacity, _ptr(segs), _ptr(reads), _ptr(raw), _ptr(total), ls.cuda_stream))
-        caller.wait_stream(ls)
+                _ptr(out), out_type, capacity, _ptr(segs), _ptr(reads), _ptr(raw), _ptr(total), ls.cuda_stream))
         return SegmentedReads(out, SegmentTable(segs), ReadSegments(reads), ReadStats(raw), total)
 
     def stitch_plan(self, segmented: SegmentedReads, length, overlap, frame_samples, capacity=None,
@@ -912,15 +630,12 @@ class PGNanoCodec:
         if not 0 <= capacity <= int(segs.shape[0]):
             raise ValueError(f"capacity must lie in [0, {int(segs.shape[0])}], the rows of the segment table")
         n = int(reads.shape[0])
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             dev = reads.device
             plan = torch.zeros((capacity, C.sizeof(_native.StitchSegment)), dtype=torch.uint8, device=dev)
             frames = torch.zeros(n + 1, dtype=torch.int64, device=dev)
             _check(self._lib.pgn_stitch_plan_device(self._h, n, _ptr(reads), _ptr(segs), capacity, C.byref(prm),
                                                     _ptr(plan), _ptr(frames), ls.cuda_stream))
-        caller.wait_stream(ls)
         return StitchPlan(StitchTable(plan), frames, prm)
 
     def stitch(self, plan: StitchPlan, rows, first_segment: int = 0, out=None, frame_base: int = 0,
@@ -966,13 +681,10 @@ class PGNanoCodec:
             _require_device(out, "out", self.device)
             if out.dtype != rows.dtype or tuple(out.shape[1:]) != frame_shape or out.dim() < 1 or not out.is_contiguous():
                 raise ValueError(f"out must be a contiguous [frames{''.join(', %d' % d for d in frame_shape)}] tensor of {rows.dtype}")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             _check(self._lib.pgn_stitch_rows_device(
                 self._h, C.byref(prm), _ptr(plan.segments.raw), first_segment, N, _ptr(rows), int(rows.stride(nd)) * item,
                 int(rows.stride(td)) * item, frame_bytes, _ptr(out), frame_base, int(out.shape[0]), ls.cuda_stream))
-        caller.wait_stream(ls)
         return out
 
     def _decode_outputs(self, read_frames, frames, capacity, base_frame, dev):
@@ -1018,9 +730,7 @@ class PGNanoCodec:
             raise ValueError("frame_base must lie in [0, 2^62)")
         item = frames.element_size()
         stride = max(int(frames.stride(0)), C_) * item
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             dev = frames.device
             n, capacity, seq, bases, status, bf = self._decode_outputs(read_frames, F, capacity, base_frame, dev)
             bs = torch.empty(capacity, dtype=torch.float32, device=dev) if base_score else None
@@ -1028,7 +738,6 @@ class PGNanoCodec:
             _check(self._lib.pgn_ctc_decode_device(
                 self._h, C.byref(prm), n, _ptr(read_frames), _ptr(frames) if F else 0, stride, frame_base, F, _ptr(seq),
                 capacity, _ptr(bases), _ptr(status), _ptr(bf), _ptr(bs), _ptr(cd), ls.cuda_stream))
-        caller.wait_stream(ls)
         return DecodedReads(seq, bases, status, bf, bs, cd, prm)
 
     def collapse_codes(self, codes, read_frames, alphabet, *, frame_base: int = 0, capacity=None,
@@ -1046,15 +755,12 @@ class PGNanoCodec:
         frame_base, F = int(frame_base), int(codes.numel())
         if not 0 <= frame_base < 1 << 62:
             raise ValueError("frame_base must lie in [0, 2^62)")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             n, capacity, seq, bases, status, bf = self._decode_outputs(read_frames, F, capacity, base_frame,
                                                                        codes.device)
             _check(self._lib.pgn_collapse_codes_device(
                 self._h, C.byref(table), n, _ptr(read_frames), _ptr(codes) if F else 0, frame_base, F, _ptr(seq), capacity,
                 _ptr(bases), _ptr(status), _ptr(bf), ls.cuda_stream))
-        caller.wait_stream(ls)
         return DecodedReads(seq, bases, status, bf, None, codes, table)
 
     def set_crf_scratch(self, nbytes: int = 0) -> None:
@@ -1102,9 +808,7 @@ class PGNanoCodec:
         if rows.stride(2) != 1 or (T > 1 and rows.stride(td) < C_) or rows.stride(nd) < 0:
             raise ValueError("the last dimension of rows must be contiguous and the frame stride at least C")
         item = rows.element_size()
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             if codes is None:
                 codes = torch.empty((N, T), dtype=torch.uint8, device=rows.device)
             else:
@@ -1117,7 +821,6 @@ class PGNanoCodec:
                 _check(self._lib.pgn_crf_viterbi_rows_device(
                     self._h, C.byref(prm), N, T, _ptr(rows), int(rows.stride(nd)) * item, int(rows.stride(td)) * item,
                     _ptr(codes), max(int(codes.stride(0)), T) if N > 1 else T, _ptr(score), ls.cuda_stream))
-        caller.wait_stream(ls)
         return CrfCodes(codes, score, prm)
 
     def decompress_reads_norm(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, *,
@@ -1142,49 +845,28 @@ class PGNanoCodec:
         import torch
 
         dtype = torch.float16 if dtype is None else dtype
-        types = {torch.float32: _native.PGN_OUT_F32, torch.float16: _native.PGN_OUT_F16}
-        if dtype not in types:
-            raise ValueError(f"dtype must be torch.float32 or torch.float16 (got {dtype})")
+        out_type = _out_type(dtype)
         prm = norm_params(mode, p, centre_mult, spread_mult, spread_floor)
         if int(max_chunk_samples) < 0:
             raise ValueError("max_chunk_samples must be >= 0 (0: no bound)")
         _require_device(blobs, "blobs", self.device)
-        nchunks = int(sample_counts.numel())
-        nreads = int(read_first_chunk.numel()) - 1
-        if nreads < 0:
-            raise ValueError("read_first_chunk needs nreads + 1 entries")
-        for t, name, want in ((out, "out", dtype), (adc, "adc", torch.int16)):
-            if t is not None:
-                _require_device(t, name, self.device)
-                if t.dtype != want:
-                    raise ValueError(f"{name} must have dtype {want} (got {t.dtype})")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        nchunks, nreads = int(sample_counts.numel()), _nreads(read_first_chunk)
+        _require_out(out, "out", self.device, dtype)
+        _require_out(adc, "adc", self.device, torch.int16)
+        with self._launch(stream) as ls:
             dev = blobs.device
-            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
-            first = read_first_chunk.to(device=dev, dtype=torch.int64).contiguous()
-            ends = torch.zeros(nchunks + 1, dtype=torch.int64, device=dev)
-            ends[1:] = torch.cumsum(counts.to(torch.int64), 0)
-            if read_out_offsets is None:
-                ro = ends[first[:-1]].contiguous()  # packed: a read starts where its first chunk would
-            else:
-                ro = read_out_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            if out is None:
-                out = torch.empty(max(int(ends[-1].item()), 1), dtype=dtype, device=dev)
+            counts, first, ro, out, bo, bs = _read_arrays(blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk,
+                                                          out, read_out_offsets, dtype)
             if adc is None and dtype == torch.float32:
                 work = torch.empty(out.numel(), dtype=torch.int16, device=dev)
             else:
                 work = adc
-            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
             status = torch.full((nchunks,), -1, dtype=torch.int32, device=dev)
             raw = torch.zeros((nreads, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
             _check(self._lib.pgn_decompress_reads_device_norm(
                 self._h, self._pa_codec, int(max_chunk_samples), nreads, nchunks, _ptr(first), _ptr(blobs), _ptr(bo),
-                _ptr(bs), _ptr(counts), _ptr(out), types[dtype], _ptr(ro), _ptr(work), C.byref(prm), _ptr(raw),
+                _ptr(bs), _ptr(counts), _ptr(out), out_type, _ptr(ro), _ptr(work), C.byref(prm), _ptr(raw),
                 _ptr(status), ls.cuda_stream))
-        caller.wait_stream(ls)
         return out, ro, ReadStats(raw), status
 
     def decompress_reads_pa(self, blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk, cal_offset=None,
@@ -1204,51 +886,29 @@ class PGNanoCodec:
         import torch
 
         dtype = torch.float32 if dtype is None else dtype
-        types = {torch.int16: _native.PGN_OUT_INT16, torch.float32: _native.PGN_OUT_F32,
-                 torch.float16: _native.PGN_OUT_F16}
-        if dtype not in types:
-            raise ValueError(f"dtype must be torch.float32, torch.float16 or torch.int16 (got {dtype})")
+        out_type = _out_type(dtype, int16=True)
         if int(max_chunk_samples) < 0:
             raise ValueError("max_chunk_samples must be >= 0 (0: no bound)")
         _require_device(blobs, "blobs", self.device)
-        nchunks = int(sample_counts.numel())
-        nreads = int(read_first_chunk.numel()) - 1
-        if nreads < 0:
-            raise ValueError("read_first_chunk needs nreads + 1 entries")
-        if out is not None:
-            _require_device(out, "out", self.device)
-            if out.dtype != dtype:
-                raise ValueError(f"out must have dtype {dtype} (got {out.dtype})")
+        nchunks, nreads = int(sample_counts.numel()), _nreads(read_first_chunk)
+        _require_out(out, "out", self.device, dtype)
         calibrated = dtype != torch.int16
         if calibrated:
             for t, name in ((cal_offset, "cal_offset"), (cal_scale, "cal_scale")):
                 if t is None or int(t.numel()) != nreads:
                     raise ValueError(f"{name} must have one entry per read ({nreads})")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        with self._launch(stream) as ls:
             dev = blobs.device
-            counts = sample_counts.to(device=dev, dtype=torch.int32).contiguous()
-            first = read_first_chunk.to(device=dev, dtype=torch.int64).contiguous()
-            ends = torch.zeros(nchunks + 1, dtype=torch.int64, device=dev)
-            ends[1:] = torch.cumsum(counts.to(torch.int64), 0)
-            if read_out_offsets is None:
-                ro = ends[first[:-1]].contiguous()  # packed: a read starts where its first chunk would
-            else:
-                ro = read_out_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            if out is None:
-                out = torch.empty(max(int(ends[-1].item()), 1), dtype=dtype, device=dev)
-            bo = blob_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            bs = blob_sizes.to(device=dev, dtype=torch.int64).contiguous()
-            co = cal_offset.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
-            cs = cal_scale.to(device=dev, dtype=torch.float32).contiguous() if calibrated else None
+            counts, first, ro, out, bo, bs = _read_arrays(blobs, blob_offsets, blob_sizes, sample_counts, read_first_chunk,
+                                                          out, read_out_offsets, dtype)
+            co = _to(cal_offset if calibrated else None, dev, torch.float32)
+            cs = _to(cal_scale if calibrated else None, dev, torch.float32)
             status = torch.full((nchunks,), -1, dtype=torch.int32, device=dev)
             read_status = torch.full((nreads,), -1, dtype=torch.int32, device=dev)
             _check(self._lib.pgn_decompress_reads_device_pa(
                 self._h, self._pa_codec, int(max_chunk_samples), nreads, nchunks, _ptr(first), _ptr(blobs), _ptr(bo),
-                _ptr(bs), _ptr(counts), _ptr(out), types[dtype], _ptr(ro), _ptr(co), _ptr(cs), _ptr(read_status),
+                _ptr(bs), _ptr(counts), _ptr(out), out_type, _ptr(ro), _ptr(co), _ptr(cs), _ptr(read_status),
                 _ptr(status), ls.cuda_stream))
-        caller.wait_stream(ls)
         return out, ro, read_status, status
 
     def reads_status(self, read_first_chunk, chunk_status, stream: int | None = None):
@@ -1257,18 +917,12 @@ class PGNanoCodec:
         import torch
 
         _require_device(chunk_status, "chunk_status", self.device)
-        nreads = int(read_first_chunk.numel()) - 1
-        if nreads < 0:
-            raise ValueError("read_first_chunk needs nreads + 1 entries")
-        caller = torch.cuda.current_stream()
-        ls = self._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        nreads = _nreads(read_first_chunk)
+        with self._launch(stream) as ls:
             dev = chunk_status.device
-            first = read_first_chunk.to(device=dev, dtype=torch.int64).contiguous()
-            cs = chunk_status.to(dtype=torch.int32).contiguous()
+            first, cs = _to(read_first_chunk, dev, torch.int64), _to(chunk_status, dev, torch.int32)
             out = torch.full((nreads,), -1, dtype=torch.int32, device=dev)
             _check(self._lib.pgn_reads_status_device(self._h, nreads, _ptr(first), _ptr(cs), _ptr(out), ls.cuda_stream))
-        caller.wait_stream(ls)
         return out
 
     def synth_reads(self, nreads: int, samples_per_read, seed: int = 42, first_read: int = 0, read_stride: int = 1,
@@ -1282,9 +936,7 @@ class PGNanoCodec:
             counts = torch.full((nreads,), samples_per_read, dtype=torch.int32, device=dev)
         else:
             counts = torch.as_tensor(samples_per_read, dtype=torch.int32, device=dev)
-        offs = torch.zeros(nreads, dtype=torch.int64, device=dev)
-        if nreads > 1:
-            offs[1:] = torch.cumsum(counts.to(torch.int64), 0)[:-1]
+        offs = _packed_offsets(nreads, counts)
         total = int(counts.to(torch.int64).sum().item())
         if out is None:
             out = torch.empty(max(total, 1), dtype=torch.int16, device=dev)

@@ -1,0 +1,331 @@
+"""The host side of the device stages: every rule of include/pgnano_hip.h as NumPy code, and the parameter
+structs of the C ABI built from Python values.
+
+Each ``*_signal`` function is the model of one device stage for one read (or one row): the same arithmetic in
+the same number formats, so a :class:`~rawnanoporesignalcompression_amd.codec.PGNanoCodec` method is held to
+it bit for bit.  The two ``*_bound`` functions size a batch's outputs on the host, :func:`select_parts` is the
+plan of a long read's selection, and the ``*_params`` builders check their values and fill the structs of
+``_native``; the defaults of the API live in them, the C ABI has none.
+
+This module needs NumPy and ctypes alone: it never loads the native library and never touches a device, so a
+consumer can check a pipeline's results where there is no GPU.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native
+
+
+# ---- calibration and per-read normalisation ----------------------------------------------------------------
+def calibrate_signal(adc, offset, scale, dtype=np.float32):
+    """The calibrated signal of int16 ADC counts on the host, ``pA = (adc + offset) * scale`` in float32
+    (the reference reader's ``Read.calibrate_signal_array``, pod5/python/pod5/src/pod5/reader.py:356-368):
+    the int16 converted exactly, one float32 add, one float32 multiply; ``dtype=np.float16`` rounds that
+    value once.  :meth:`PGNanoCodec.decompress_batch_pa` writes these bits from the decode kernels."""
+    pa = (np.asarray(adc, dtype=np.int16).astype(np.float32) + np.float32(offset)) * np.float32(scale)
+    return pa if np.dtype(dtype) == np.float32 else pa.astype(dtype)
+
+
+def normalise_signal(adc, centre, spread, dtype=np.float32):
+    """The normalised signal on the host, ``(adc + (-centre)) * (1 / spread)`` in float32: the int16
+    converted exactly, one float32 division for the reciprocal, one add, one multiply;
+    ``dtype=np.float16`` rounds that value once.  :meth:`PGNanoCodec.decompress_reads_norm` writes these bits."""
+    inv = np.float32(1.0) / np.float32(spread)
+    return calibrate_signal(adc, -np.float32(centre), inv, dtype)
+
+
+def norm_params(mode="quantile", p=(0.2, 0.9), centre_mult=0.51, spread_mult=0.53, spread_floor=1.0):
+    """``pgn_norm_params`` from Python values (the defaults live here; the C ABI has none)."""
+    if mode not in _native.NORM_MODES:
+        raise ValueError(f"mode must be one of {sorted(_native.NORM_MODES)} (got {mode!r})")
+    return _native.NormParams(_native.NORM_MODES[mode], 0, float(p[0]), float(p[1]), float(centre_mult),
+                              float(spread_mult), float(spread_floor), 0.0)
+
+
+def _host_stats(y, prm):
+    """(centre, spread) of one read on the host, as the per-read normalisation section defines them."""
+    f32 = np.float32
+    s = np.sort(y.astype(np.int64))
+    n = s.size
+    if prm.mode == _native.PGN_NORM_QUANTILE:
+        a = int(s[int(np.floor(np.float64(prm.p_lo) * np.float64(n - 1)))])
+        b = int(s[int(np.floor(np.float64(prm.p_hi) * np.float64(n - 1)))])
+        centre, spread = f32(prm.centre_mult) * f32(a + b), f32(prm.spread_mult) * f32(b - a)
+    else:
+        m2 = int(s[(n - 1) // 2] + s[n // 2])
+        t = np.sort(np.abs(2 * y.astype(np.int64) - m2))
+        centre = f32(0.5) * f32(m2)
+        spread = f32(prm.spread_mult) * (f32(0.25) * f32(int(t[(n - 1) // 2] + t[n // 2])))
+    return centre, max(spread, f32(prm.spread_floor))
+
+
+# ---- long reads ----------------------------------------------------------------------------------------------
+def select_parts(n: int, split_min_samples: int, part_samples: int):
+    """The plan of one read's selection on the host (include/pgnano_hip.h, "Long reads"): the boundaries of
+    the parts a read of ``n`` samples is selected in under :meth:`PGNanoCodec.set_select_split`'s settings, as
+    ``parts + 1`` ascending uint64 values from 0 to ``n``.  A read that is not split has one part."""
+    n, split_min_samples, part_samples = int(n), int(split_min_samples), int(part_samples)
+    if not (1024 <= part_samples <= 1 << 24 and part_samples <= split_min_samples < 1 << 32) or n < 0:
+        raise ValueError("need 1024 <= part_samples <= 2**24 and part_samples <= split_min_samples < 2**32")
+    parts = 1
+    if split_min_samples < n < 1 << 32:
+        parts = min(-(-n // part_samples), _native.PGN_SELECT_MAX_PARTS)
+    return np.array([j * n // parts for j in range(parts + 1)], dtype=np.uint64)
+
+
+# ---- trim and segments -----------------------------------------------------------------------------------------
+def trim_params(max_samples=8000, window=40, min_elements=3, min_trim=10, mad_mult=1.4826, threshold_mads=2.4):
+    """``pgn_trim_params`` from Python values (the usual values live here; the C ABI has none).
+    ``max_samples=0`` turns trimming off."""
+    return _native.TrimParams(int(max_samples), int(window), int(min_elements), int(min_trim), float(mad_mult),
+                              float(threshold_mads))
+
+
+def _trim_struct(trim):
+    """None / False: trimming off; True: the usual values; a dict: :func:`trim_params` of it; or the struct."""
+    if trim is None or trim is False:
+        return trim_params(max_samples=0)
+    if trim is True:
+        return trim_params()
+    if isinstance(trim, _native.TrimParams):
+        return trim
+    return trim_params(**trim)
+
+
+def segment_params(length, overlap):
+    """``pgn_segment_params``: rows of ``length`` elements, neighbours sharing ``overlap`` of them."""
+    length, overlap = int(length), int(overlap)
+    if not (1 <= length <= 1 << 24 and 0 <= overlap < length):
+        raise ValueError(f"need 1 <= length <= 2^24 and 0 <= overlap < length (got {length}, {overlap})")
+    return _native.SegmentParams(length, overlap)
+
+
+def _segment_starts(m: int, length: int, overlap: int):
+    """[(start, valid)] of a trimmed read of m samples (include/pgnano_hip.h, "Segments")."""
+    stride = length - overlap
+    if m == 0:
+        return []
+    if m <= length:
+        return [(0, m)]
+    k = -(-(m - length) // stride) + 1
+    return [(min(j * stride, m - length), length) for j in range(k)]
+
+
+def segment_bound(counts, length, overlap) -> int:
+    """The segments a batch of reads of these (untrimmed) lengths can need: trimming only shortens a read
+    and the count does not decrease with the length, so this is an upper bound, computed on the host."""
+    p = segment_params(length, overlap)
+    n = np.asarray(counts).astype(np.int64).reshape(-1)
+    stride = p.length - p.overlap
+    k = np.where(n > p.length, (np.maximum(n - p.length, 0) + stride - 1) // stride + 1, (n > 0).astype(np.int64))
+    return int(k.sum())
+
+
+def trim_signal(adc, **trim) -> int:
+    """The head trim of one read on the host (include/pgnano_hip.h, "Trim"): the samples to drop.
+    ``**trim`` as in :func:`trim_params`."""
+    T = trim_params(**trim)
+    x = np.asarray(adc, dtype=np.int16).reshape(-1)
+    n = x.size
+    if T.max_samples == 0:
+        return 0
+    H = min(n, T.max_samples)
+    if H < T.min_trim + T.window:
+        return min(T.min_trim, n)
+    v = x[:H].astype(np.int64)
+    s = np.sort(v)
+    m2 = int(s[(H - 1) // 2] + s[H // 2])
+    t = np.sort(np.abs(2 * v - m2))
+    mad4 = int(t[(H - 1) // 2] + t[H // 2])
+    f32 = np.float32
+    thr = f32(0.5) * f32(m2) + f32(T.threshold_mads) * (f32(T.mad_mult) * (f32(0.25) * f32(mad4)))
+    above = x[:H].astype(np.float32) > thr
+    seen = False
+    for w in range((H - T.min_trim) // T.window):
+        e = T.min_trim + (w + 1) * T.window
+        seen = seen or int(above[e - T.window:e].sum()) > T.min_elements
+        if seen and not above[e - 1]:
+            return e if e < H else T.min_trim
+    return T.min_trim
+
+
+def segment_signal(adc, length, overlap, trim=None, dtype=np.float16, **norm):
+    """The model segments of one read on the host, ``[segments, length]``: the read without its trimmed head
+    (``trim`` as in :meth:`PGNanoCodec.segment_reads`), normalised by its own statistics (``**norm`` as in
+    :func:`norm_params`; :func:`normalise_signal`'s arithmetic), cut into rows that overlap by ``overlap``, the
+    last aligned to the read's end, a short read padded with +0.0.  :meth:`PGNanoCodec.segment_reads` writes
+    these bits."""
+    p = segment_params(length, overlap)
+    prm = norm_params(**norm)
+    T = _trim_struct(trim)
+    x = np.asarray(adc, dtype=np.int16).reshape(-1)
+    y = x[trim_signal(x, **{f: getattr(T, f) for f, _ in T._fields_}):]
+    plan = _segment_starts(y.size, p.length, p.overlap)
+    rows = np.zeros((len(plan), p.length), dtype)
+    if plan:
+        centre, spread = _host_stats(y, prm)
+        with np.errstate(over="ignore"):  # binary16 overflow is +-inf, as on the device
+            z = normalise_signal(y, centre, spread, dtype)
+        for j, (start, valid) in enumerate(plan):
+            rows[j, :valid] = z[start:start + valid]
+    return rows
+
+
+# ---- model output back to reads ---------------------------------------------------------------------------------
+def stitch_params(length, overlap, frame_samples):
+    """``pgn_stitch_params``: the ``length`` and ``overlap`` the segments were cut with and the model's stride
+    ``frame_samples``, which divides ``length`` and does not exceed ``length - overlap``."""
+    L, V, s = int(length), int(overlap), int(frame_samples)
+    if not (1 <= s and 1 <= L <= 1 << 24 and L % s == 0 and 0 <= V and s <= L - V):
+        raise ValueError("need 1 <= frame_samples, length % frame_samples == 0, 0 <= overlap, frame_samples <= "
+                         f"length - overlap and length <= 2^24 (got {L}, {V}, {s})")
+    return _native.StitchParams(L, V, s, 0)
+
+
+def stitch_plan_signal(m_or_segments, length, overlap, frame_samples):
+    """The kept frames of one read's segments on the host (include/pgnano_hip.h, "Model output back to
+    reads"): ``[segments, 2]`` int64, ``first`` and ``count`` per segment.  ``m_or_segments`` is the trimmed
+    read's length, or its segments as ``(start, valid)`` rows of the segment table (any common origin of the
+    starts).  :meth:`PGNanoCodec.stitch_plan` writes these values for a read that is taken."""
+    p = stitch_params(length, overlap, frame_samples)
+    L, s, T = p.length, p.frame_samples, p.length // p.frame_samples
+    segs = _segment_starts(int(m_or_segments), L, p.overlap) if np.isscalar(m_or_segments) else m_or_segments
+    segs = np.asarray(segs, dtype=np.int64).reshape(-1, 2)
+    k = segs.shape[0]
+    if k == 0:
+        return np.zeros((0, 2), np.int64)
+    a, valid = segs[:, 0] - segs[0, 0], segs[:, 1]
+    half = (a[:-1] + L - a[1:]) // 2           # half the overlap of segments j and j + 1, rounded down
+    lo = np.concatenate([[0], half])           # c_{j-1} - a_j
+    hi = np.concatenate([a[1:] - a[:-1] + half, valid[-1:]])  # c_j - a_j
+    first = np.minimum(-(-lo // s), T)
+    end = np.minimum(-(-hi // s), T)
+    return np.stack([first, np.maximum(end - first, 0)], 1)
+
+
+def stitch_bound(counts, length, overlap, frame_samples) -> int:
+    """The frames a batch of reads of these (untrimmed) lengths can give: ``ceil(n / s) + segments(n)`` per
+    read bounds the frames of every trimmed length, so this is an upper bound computed on the host."""
+    p = stitch_params(length, overlap, frame_samples)
+    n = np.asarray(counts).astype(np.int64).reshape(-1)
+    return int((-(-n // p.frame_samples)).sum()) + segment_bound(n, p.length, p.overlap)
+
+
+# ---- stitched frames to bases (CTC) -----------------------------------------------------------------------------
+def _alphabet_bytes(alphabet, entries):
+    a = alphabet.encode("latin-1") if isinstance(alphabet, str) else bytes(bytearray(alphabet))
+    if len(a) > entries:
+        raise ValueError(f"alphabet has {len(a)} entries, at most {entries} fit")
+    return a
+
+
+def ctc_params(classes, blank=0, alphabet="NACGT", dtype=np.float16):
+    """``pgn_ctc_params``: ``classes`` scores per frame (2..64) of ``dtype`` (float16 or float32), class
+    ``blank`` emits nothing, class ``c`` writes ``alphabet[c]`` (one byte per class)."""
+    C_, blank = int(classes), int(blank)
+    a = _alphabet_bytes(alphabet, 64)
+    types = {np.dtype(np.float32): _native.PGN_OUT_F32, np.dtype(np.float16): _native.PGN_OUT_F16}
+    if not (2 <= C_ <= 64 and 0 <= blank < C_):
+        raise ValueError(f"need 2 <= classes <= 64 and 0 <= blank < classes (got {C_}, {blank})")
+    if len(a) != C_:
+        raise ValueError(f"alphabet must have one entry per class ({C_}), got {len(a)}")
+    if np.dtype(dtype) not in types:
+        raise ValueError("scores must be float16 or float32")
+    return _native.CtcParams(C_, blank, types[np.dtype(dtype)], 0, (C.c_uint8 * 64)(*a))
+
+
+def collapse_codes_signal(codes, alphabet):
+    """The bases of one read's code bytes on the host (include/pgnano_hip.h, "Stitched frames to bases"): a
+    frame emits iff bit 7 of its code is set, and its base is ``alphabet[code & 0x7f]``.  Returns ``(seq,
+    base_frame)``: uint8 bases and the uint32 frame of each."""
+    codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+    table = np.zeros(128, np.uint8)
+    a = _alphabet_bytes(alphabet, 128)
+    table[:len(a)] = np.frombuffer(a, np.uint8)
+    at = np.flatnonzero(codes & 0x80)
+    return table[codes[at] & 0x7F], at.astype(np.uint32)
+
+
+def ctc_decode_signal(scores, alphabet="NACGT", blank=0):
+    """The best-path CTC decode of one read's ``[frames, classes]`` scores on the host (include/pgnano_hip.h,
+    "Stitched frames to bases"): the label of a frame is ``np.argmax`` of its scores, a frame emits iff its
+    label is not ``blank`` and it is the read's first frame or its label differs from the frame before.
+    Returns ``(seq, base_frame, base_score, codes)``: uint8 bases, the uint32 frame and the float32 winning
+    score of each, and one code byte per frame (the label, bit 7 set where the frame emits).
+    :meth:`PGNanoCodec.ctc_decode` writes these values for a read that is taken."""
+    scores = np.asarray(scores)
+    if scores.ndim != 2:
+        raise ValueError("scores must be [frames, classes]")
+    prm = ctc_params(scores.shape[1], blank, alphabet, scores.dtype)
+    if scores.shape[0] == 0:
+        return np.zeros(0, np.uint8), np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, np.uint8)
+    labels = np.argmax(scores, axis=1)
+    emit = labels != prm.blank
+    emit[1:] &= labels[1:] != labels[:-1]
+    codes = (labels | np.where(emit, 0x80, 0)).astype(np.uint8)
+    seq, at = collapse_codes_signal(codes, bytes(prm.alphabet))
+    return seq, at, scores[at, labels[at]].astype(np.float32), codes
+
+
+# ---- model rows to per-frame codes (CRF) ------------------------------------------------------------------------
+def crf_params(state_len, transitions=5, dtype=np.float16, stay_score=0.0):
+    """``pgn_crf_params``: ``4 ** state_len`` states (``state_len`` in 1..5) with ``transitions`` scores each
+    per frame, of ``dtype`` (float16 or float32): 5 is a stay and four moves, 4 is the four moves with every
+    stay scoring the constant ``stay_score`` (which must be +0.0 with 5)."""
+    k, tr = int(state_len), int(transitions)
+    types = {np.dtype(np.float32): _native.PGN_OUT_F32, np.dtype(np.float16): _native.PGN_OUT_F16}
+    if not 1 <= k <= 5:
+        raise ValueError(f"state_len must lie in 1..5 (got {k})")
+    if tr not in (4, 5):
+        raise ValueError(f"transitions must be 4 or 5 (got {tr})")
+    if np.dtype(dtype) not in types:
+        raise ValueError("scores must be float16 or float32")
+    stay = np.float32(stay_score)
+    if tr == 5 and stay.view(np.uint32) != 0:
+        raise ValueError("stay_score must be +0.0 with transitions == 5 (the stay scores are the model's)")
+    return _native.CrfParams(k, tr, types[np.dtype(dtype)], float(stay))
+
+
+def crf_viterbi_signal(scores, state_len, transitions=5, stay_score=0.0):
+    """The best-path decode of one row's ``[T, C]`` CRF scores on the host (include/pgnano_hip.h, "Model rows to
+    per-frame codes (CRF)"), ``C = transitions * 4 ** state_len``: float32 adds and ``>`` alone, a loop over the
+    frames vectorised over the states.  Returns ``(codes, row_score)``: one uint8 per frame (the newest base of
+    the frame's state, bit 7 set where the path moves into it) and the float32 score of the path.
+    :meth:`PGNanoCodec.crf_viterbi` writes these values for every row."""
+    scores = np.asarray(scores)
+    if scores.ndim != 2:
+        raise ValueError("scores must be [T, C]")
+    prm = crf_params(state_len, transitions, scores.dtype, stay_score)
+    tr, S = prm.transitions, 4 ** prm.state_len
+    T = scores.shape[0]
+    if scores.shape[1] != tr * S or not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
+        raise ValueError(f"scores must be [T, {tr * S}] with 1 <= T <= 2^24 (got {scores.shape})")
+    x = scores.astype(np.float32).reshape(T, S, tr)
+    pred = (np.arange(4)[:, None] * S + np.arange(S)[None, :]) >> 2  # p(s, b) as [b, s]
+    stay = np.float32(prm.stay_score)
+    a = np.zeros(S, np.float32)
+    bp = np.zeros((T, S), np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(T):
+            best = a + (x[t, :, 0] if tr == 5 else stay)
+            for b in range(4):
+                cand = a[pred[b]] + x[t, :, tr - 4 + b]
+                take = cand > best
+                best = np.where(take, cand, best)
+                bp[t, take] = 1 + b
+            a = best
+        e, m = 0, a[0]
+        for s in range(1, S):
+            if a[s] > m:
+                e, m = s, a[s]
+    codes = np.zeros(T, np.uint8)
+    s = e
+    for t in range(T - 1, -1, -1):
+        j = int(bp[t, s])
+        codes[t] = (s & 3) | (0x80 if j else 0)
+        if j:
+            s = ((j - 1) * S + s) >> 2
+    return codes, np.float32(m)

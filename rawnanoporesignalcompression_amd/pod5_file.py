@@ -230,8 +230,8 @@ class Pod5File:
         caller's current stream."""
         import torch
 
-        from .codec import ReadStats, _require_device
-        from .codec import norm_params as make_norm
+        from .codec import PGNanoError, ReadStats, _out_type, _require_out
+        from .host import norm_params as make_norm
 
         if output not in _native.LOAD_KINDS:
             raise ValueError(f"output must be one of {sorted(_native.LOAD_KINDS)} (got {output!r})")
@@ -243,8 +243,6 @@ class Pod5File:
         if norm_params and output != "norm":
             raise ValueError(f"normalisation parameters {sorted(norm_params)} need output='norm'")
         prm = make_norm(**norm_params) if output == "norm" else None
-        types = {torch.int16: _native.PGN_OUT_INT16, torch.float32: _native.PGN_OUT_F32,
-                 torch.float16: _native.PGN_OUT_F16}
         # the reads' lengths, on the host
         _, samples = self.row_columns()
         if row_lists is not None:
@@ -286,14 +284,9 @@ class Pod5File:
                 raise ValueError(f"out_offsets must have one entry per read ({nreads})")
             need = int((offs + counts).max()) if nreads else 0
         dev = torch.device("cuda", codec.device)
-        for t, name, want in ((out, "out", dtype), (adc, "adc", torch.int16)):
-            if t is not None:
-                _require_device(t, name, codec.device)
-                if t.dtype != want:
-                    raise ValueError(f"{name} must have dtype {want} (got {t.dtype})")
-        caller = torch.cuda.current_stream()
-        ls = codec._launch_stream(stream)
-        with torch.cuda.stream(ls):
+        _require_out(out, "out", codec.device, dtype)
+        _require_out(adc, "adc", codec.device, torch.int16)
+        with codec._launch(stream) as ls:
             if out is None:
                 out = torch.empty(max(need, 1), dtype=dtype, device=dev)
             if adc is None and output == "norm" and dtype == torch.float32:
@@ -302,7 +295,7 @@ class Pod5File:
             raw = (torch.zeros((nreads, C.sizeof(_native.ReadStats)), dtype=torch.uint8, device=dev)
                    if output == "norm" else None)
             got_off, got_n = np.zeros(nreads, np.uint64), np.zeros(nreads, np.uint64)
-            args = _native.LoadArgs(_native.LOAD_KINDS[output], types[dtype], _native.VARIANTS[codec.variant], 0,
+            args = _native.LoadArgs(_native.LOAD_KINDS[output], _out_type(dtype, int16=True), _native.VARIANTS[codec.variant], 0,
                                     C.pointer(prm) if prm is not None else None, out.data_ptr(), out.numel(),
                                     _ptr(offs) or None, adc.data_ptr() if adc is not None else None,
                                     raw.data_ptr() if raw is not None and nreads else None,
@@ -316,10 +309,7 @@ class Pod5File:
                 sel_ptr = None if idx is None else (idx if idx.size else np.zeros(1, np.uint64)).ctypes.data
                 rc = lib.pgn_pod5_load_reads_device(codec._h, self._h, sel_ptr, nreads, C.byref(args), ls.cuda_stream)
             if rc:
-                from .codec import PGNanoError
-
                 raise PGNanoError(rc, lib.pgn_pod5_last_error().decode(errors="replace"))
-        caller.wait_stream(ls)
         return LoadedReads(out, got_off, got_n, status, ReadStats(raw) if raw is not None else None, adc)
 
     def load_segments(self, codec, reads=None, *, length, overlap, trim=None, dtype=None, **norm_params):
