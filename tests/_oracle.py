@@ -103,6 +103,37 @@ def zstd_compress_ex(data, level: int, window_log: int = 0) -> bytes:
     return out[:r].tobytes()
 
 
+def zstd_decompress(frame: bytes, cap: int) -> bytes | None:
+    """libzstd's decode of one frame into at most cap bytes; None where it fails."""
+    L = oracle()
+    a = _buf(frame)
+    out = np.zeros(max(cap, 1), np.uint8)
+    r = L.pgno_zstd_decompress(a.ctypes.data, len(frame), out.ctypes.data, cap)
+    return None if r > cap else out[:r].tobytes()
+
+
+def blob_frames(blob: bytes, nframes: int) -> list[bytes] | None:
+    """The zstd frames of a blob: nframes - 1 behind u64 length prefixes, the last one to the end (the inverse
+    of variant_assemble; VBZ and VBZ0: the blob is the one frame).  None where a prefix runs past the blob."""
+    p, frames = 0, []
+    for _ in range(nframes - 1):
+        if p + 8 > len(blob):
+            return None
+        sz = int.from_bytes(blob[p:p + 8], "little")
+        if sz > len(blob) - p - 8:
+            return None
+        frames.append(blob[p + 8:p + 8 + sz])
+        p += 8 + sz
+    frames.append(blob[p:])
+    return frames
+
+
+def blob_streams(blob: bytes, nframes: int, n: int) -> list[bytes | None] | None:
+    """blob -> frames -> the raw streams (libzstd on the host); a stream of n samples has at most 3 n + 32 bytes"""
+    frames = blob_frames(blob, nframes)
+    return None if frames is None else [zstd_decompress(f, 3 * n + 32) for f in frames]
+
+
 def c5_streams(x: np.ndarray) -> list[bytes]:
     """The five raw C5 streams [keys, S, M, Llow, Lhigh] of one chunk (C5.hpp:282-415)."""
     L = oracle()
