@@ -591,7 +591,8 @@ int pgn_stitch_rows_device(pgn_ctx *ctx, const pgn_stitch_params *params, const 
  * element size; nreads >= 2^32 or frame_capacity >= 2^40; a NULL d_read_bases; with nreads > 0 a NULL
  * d_read_frames or d_read_status; with frame_capacity > 0 a NULL d_frames (d_codes in the collapse call); with
  * base_capacity > 0 a NULL d_seq.  With nreads == 0 only d_read_bases[0] = 0 is written.
- * Not covered: transducer decoding and beam search; quality strings (phred calibration); bfloat16 scores. */
+ * Not covered: transducer decoding and beam search; quality strings for this path (pgn_base_qual_device makes
+ * them of posterior marginals, which a best-path CTC decode does not have); bfloat16 scores. */
 #define PGN_CTC_TILE_FRAMES 1024
 typedef struct pgn_ctc_params {
     uint32_t classes;       /* C, 2..64 */
@@ -672,7 +673,8 @@ int pgn_collapse_codes_device(pgn_ctx *ctx, const uint8_t alphabet[128], size_t 
  * touches nothing.  pgn_ctx_set_crf_scratch refuses a NULL ctx.
  * Not covered: beam search, posteriors and forward-backward; quality strings; bfloat16 scores; a decode that
  * stops at a short row's valid samples (padding frames are decoded, and the stitch drops them); alphabets
- * other than 4 bases. */
+ * other than 4 bases.  That is this call's list: posteriors by forward-backward and the quality strings made of
+ * them are calls of their own, "Posteriors and qualities (CRF)" below. */
 #define PGN_CRF_DEFAULT_SCRATCH 1073741824ull
 typedef struct pgn_crf_params {
     uint32_t state_len;     /* k, 1..5: S = 4^k states */
@@ -686,6 +688,94 @@ int pgn_crf_viterbi_rows_device(pgn_ctx *ctx, const pgn_crf_params *params, uint
                                 const void *d_rows, uint64_t row_stride_bytes, uint64_t frame_stride_bytes,
                                 uint8_t *d_codes, uint64_t codes_row_stride, float *d_row_score /* may be NULL */,
                                 void *stream);
+
+/* ---- Posteriors and qualities (CRF) ---------------------------------------------------------------------
+ * The posterior marginals of a CRF model's rows by a log-sum-exp forward-backward pass over the rows
+ * pgn_crf_viterbi_rows_device reads, and, once both are stitched, one phred character per called base:
+ *   segment -> model -> pgn_crf_viterbi_rows_device and pgn_crf_posterior_rows_device
+ *     -> pgn_stitch_rows_device of the codes (frame_bytes = 1) and of the probabilities (frame_bytes = 16)
+ *     -> pgn_collapse_codes_device -> pgn_base_qual_device
+ * is a route to FASTQ records.  No outside source defines the rules, so this text does.
+ *
+ * pgn_crf_posterior_rows_device.  Parameters, states, p(s, b), stay and move(t, s, b) are those of "Model rows to
+ * per-frame codes (CRF)".  With
+ *   c(u, n) = ((u << 2) | n) & (S - 1)   and   top(u) = u >> (2k - 2)
+ * (the state after u by a move that appends base n, and the base that move drops):
+ *   Forward   a_0[s] = 0.
+ *             a_{t+1}[s] = log( exp(a_t[s] + stay(t, s)) + sum_b exp(a_t[p(s, b)] + move(t, s, b)) ).
+ *   Backward  b_T[s] = 0.
+ *             b_t[u] = log( exp(stay(t, u) + b_{t+1}[u]) + sum_n exp(move(t, c(u, n), top(u)) + b_{t+1}[c(u, n)]) ).
+ *   Marginal of the state after frame t
+ *             g_t[s] = exp(a_{t+1}[s] + b_{t+1}[s]) / sum_s' exp(a_{t+1}[s'] + b_{t+1}[s']).
+ *   Output    post[t][b] = sum over s with (s & 3) == b of g_t[s]:
+ * the probability that the newest base of the state after frame t is b.  That state is the one whose newest base
+ * the Viterbi call writes into code_t, so post[t][code_t & 3] is the called base's marginal.
+ * Arithmetic is float32 with a renormalisation per frame: both recursions and the marginal do not change when a
+ * constant is added to a whole vector, so each step subtracts element 0 of the vector it reads, and the stored
+ * a_t and b_t stay near zero whatever T is (states differ by at most k moves' worth of score).  Every log-sum-exp
+ * takes its largest term out first.  Unlike the other model calls this one has a tolerance: crf_posteriors_signal
+ * (the package's numpy model) in float64 is the reference and its float32 form the yardstick; the device is held to
+ * 4 times the float32 form's own error, measured as max |p - p64| / max(p64, 1e-6) with a floor of 2^-20.  The
+ * domain is finite scores: for a row that holds a NaN or an infinity the values are unspecified, but no access
+ * leaves the buffers and the call ends.
+ *
+ * Frame t of row g is read as in pgn_crf_viterbi_rows_device (both [N, T, C] and [T, N, C], float16 or float32,
+ * any element-aligned pointer), and its four float32 values go to
+ *   d_post + g * post_row_stride + 4 * t        (post_row_stride in floats).
+ * Nothing else is written.  The call is asynchronous on `stream` with no host wait.
+ *
+ * Scratch is the forward vectors, one float32 per state and frame:
+ *   bytes per row = 4 * S * T
+ * on the context and under the cap of pgn_ctx_set_crf_scratch, which both calls share (as they share the memory).
+ * Rows are handled in successive groups of floor(cap / bytes per row) on the same stream, with no host wait; a
+ * single row above the cap is PGN_ERR_INVALID_ARG.  At k = 5 and T = 2,000 a row takes 8,192,000 bytes and the
+ * default cap holds 131 rows, fewer than the device has compute units: raise the cap for such batches.
+ *
+ * PGN_ERR_INVALID_ARG before any GPU call, checking in the Viterbi call's order: a NULL ctx or params; the
+ * parameter conditions; T == 0 or T > 2^24; frame_stride_bytes < C * the element size unless T == 1, or d_rows or
+ * either stride not a multiple of the element size; post_row_stride < 4 * T unless nrows <= 1, or d_post not a
+ * multiple of 4; nrows >= 2^32; a row that exceeds the scratch cap; with nrows > 0 a NULL d_rows or d_post.
+ * nrows == 0 returns PGN_OK and touches nothing.
+ *
+ * pgn_base_qual_device.  Exact: integer sums and comparisons.  The window (frame_base, frame_capacity) and the
+ * taken reads are those of pgn_collapse_codes_device, whose outputs for the same window the call reads:
+ * d_read_bases, d_base_frame, d_read_status.  d_codes[i - frame_base] is frame i's code and
+ * d_post + 4 * (i - frame_base) its four probabilities, as the rows call lays 16-byte frames.  A read gets output
+ * iff it is taken, its status is PGN_OK and read_bases[r+1] <= base_capacity (and it has fewer than 2^32 frames,
+ * which base_frame could not describe); for every other read nothing is read or written.
+ * Base g of read r: t0 = base_frame[g]; t1 = base_frame[g+1] if g + 1 < read_bases[r+1], else the read's frame
+ * count; n = t1 - t0.  With c = code_{t0} & 3, for every frame t in [t0, t1):
+ *   err_t = (post[t][(c+1)&3] + post[t][(c+2)&3]) + post[t][(c+3)&3]       in float32, in that order
+ *   u_t   = (uint64)trunc(clamp(err_t, 0, 1) * 2^32), clamped to 2^32 - 1; a NaN counts as 2^32 - 1.
+ *   U = sum of u_t (uint64; it cannot wrap), and
+ *   qual[g] = 33 + q_min + #{ j < nthresholds : U <= (uint64)thr[j] * n }.
+ * The sum has no order, so any split of a long block gives the same byte.  Frames before a read's first base belong
+ * to no base.  Parameters (pgn_qual_params): q_min + nthresholds <= 93 and thr non-increasing, else
+ * PGN_ERR_INVALID_ARG.  thr[j] is the mean error, in units of 2^-32, at or below which a base earns q_min + j + 1:
+ * the package's qual_thresholds builds floor(2^32 * 10^(-((q_min + j + 0.5) - q_shift) / (10 * q_scale))), the
+ * points where q_shift + q_scale * (-10 log10 err) rounds up.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx or params; the parameter conditions;
+ * nreads >= 2^32 or frame_capacity >= 2^40; d_post not a multiple of 4; with nreads > 0 a NULL d_read_frames,
+ * d_read_bases or d_read_status; with frame_capacity > 0 a NULL d_codes or d_post; with base_capacity > 0 a NULL
+ * d_base_frame or d_qual.  nreads == 0 returns PGN_OK and touches nothing.  Asynchronous, no host wait, no scratch.
+ *
+ * Not covered: beam search; a row's log partition function; per-read mean quality; bfloat16; alphabets other than
+ * 4 bases; qualities for the CTC path; a checkpointed backward pass (a third read of the scores for a sixteenth of
+ * the scratch). */
+typedef struct pgn_qual_params {
+    uint32_t q_min;         /* the quality of a base no threshold admits */
+    uint32_t nthresholds;   /* q_min + nthresholds <= 93 */
+    uint32_t thr[93];       /* non-increasing over the first nthresholds; the rest is not read */
+} pgn_qual_params;
+
+int pgn_crf_posterior_rows_device(pgn_ctx *ctx, const pgn_crf_params *params, uint64_t nrows, uint32_t T,
+                                  const void *d_rows, uint64_t row_stride_bytes, uint64_t frame_stride_bytes,
+                                  float *d_post, uint64_t post_row_stride, void *stream);
+
+int pgn_base_qual_device(pgn_ctx *ctx, const pgn_qual_params *params, size_t nreads, const uint64_t *d_read_frames,
+                         const uint8_t *d_codes, const float *d_post, uint64_t frame_base, uint64_t frame_capacity,
+                         const uint64_t *d_read_bases, const uint32_t *d_base_frame, const int32_t *d_read_status,
+                         uint8_t *d_qual, uint64_t base_capacity, void *stream);
 
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->

@@ -112,6 +112,14 @@ class CrfParams(C.Structure):
                 ("stay_score", C.c_float)]
 
 
+PGN_QUAL_MAX = 93  # '!' + 93 is '~'
+
+
+class QualParams(C.Structure):
+    """pgn_qual_params"""
+    _fields_ = [("q_min", C.c_uint32), ("nthresholds", C.c_uint32), ("thr", C.c_uint32 * PGN_QUAL_MAX)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -187,6 +195,11 @@ SIGNATURES = [
     ("pgn_ctx_set_crf_scratch", C.c_int, [_VP, C.c_uint64]),
     ("pgn_crf_viterbi_rows_device", C.c_int,
      [_VP, C.POINTER(CrfParams), C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _VP, _VP]),
+    ("pgn_crf_posterior_rows_device", C.c_int,
+     [_VP, C.POINTER(CrfParams), C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _VP]),
+    ("pgn_base_qual_device", C.c_int,
+     [_VP, C.POINTER(QualParams), _SZ, _U64P, _VP, _VP, C.c_uint64, C.c_uint64, _U64P, _U32P, _I32P, _VP, C.c_uint64,
+      _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

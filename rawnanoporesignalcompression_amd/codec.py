@@ -120,6 +120,29 @@ def _to(t, dev, dtype):
     return None if t is None else t.to(device=dev, dtype=dtype).contiguous()
 
 
+def _crf_rows(rows, state_len, transitions, stay_score, time_major, device):
+    """The rows argument of the CRF calls, checked: ``(pgn_crf_params, N, T, row dimension, frame dimension)``.
+    ``transitions=None`` takes 4 or 5 from the frame's size."""
+    import torch
+
+    _require_device(rows, "rows", device)
+    if rows.dim() != 3 or rows.dtype not in (torch.float16, torch.float32):
+        raise ValueError("rows must be a [N, T, C] (or [T, N, C]) tensor of float16 or float32")
+    nd, td = (1, 0) if time_major else (0, 1)
+    N, T, C_ = int(rows.shape[nd]), int(rows.shape[td]), int(rows.shape[2])
+    S = 4 ** int(state_len) if 1 <= int(state_len) <= 5 else 0
+    if transitions is None:
+        transitions = 4 if C_ == 4 * S else 5
+    prm = crf_params(state_len, transitions, np.float16 if rows.dtype == torch.float16 else np.float32, stay_score)
+    if C_ != prm.transitions * S:
+        raise ValueError(f"rows must have {prm.transitions * S} scores per frame (got {C_})")
+    if not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
+        raise ValueError("rows must have between 1 and 2^24 frames")
+    if rows.stride(2) != 1 or (T > 1 and rows.stride(td) < C_) or rows.stride(nd) < 0:
+        raise ValueError("the last dimension of rows must be contiguous and the frame stride at least C")
+    return prm, N, T, nd, td
+
+
 def _packed_offsets(n: int, sizes):
     """Where each of ``n`` chunks starts when they lie end to end: the sum of the ``sizes`` (counts or
     capacities) before it, int64."""
@@ -792,21 +815,7 @@ class PGNanoCodec:
         """
         import torch
 
-        _require_device(rows, "rows", self.device)
-        if rows.dim() != 3 or rows.dtype not in (torch.float16, torch.float32):
-            raise ValueError("rows must be a [N, T, C] (or [T, N, C]) tensor of float16 or float32")
-        nd, td = (1, 0) if time_major else (0, 1)
-        N, T, C_ = int(rows.shape[nd]), int(rows.shape[td]), int(rows.shape[2])
-        S = 4 ** int(state_len) if 1 <= int(state_len) <= 5 else 0
-        if transitions is None:
-            transitions = 4 if C_ == 4 * S else 5
-        prm = crf_params(state_len, transitions, np.float16 if rows.dtype == torch.float16 else np.float32, stay_score)
-        if C_ != prm.transitions * S:
-            raise ValueError(f"rows must have {prm.transitions * S} scores per frame (got {C_})")
-        if not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
-            raise ValueError("rows must have between 1 and 2^24 frames")
-        if rows.stride(2) != 1 or (T > 1 and rows.stride(td) < C_) or rows.stride(nd) < 0:
-            raise ValueError("the last dimension of rows must be contiguous and the frame stride at least C")
+        prm, N, T, nd, td = _crf_rows(rows, state_len, transitions, stay_score, time_major, self.device)
         item = rows.element_size()
         with self._launch(stream) as ls:
             if codes is None:

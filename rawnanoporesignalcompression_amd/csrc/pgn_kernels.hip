@@ -22,6 +22,8 @@
 #include "pgn_stitch.h"
 #include "pgn_ctc.h"
 #include "pgn_crf.h"
+#include "pgn_crf_post.h"
+#include "pgn_qual.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2133,7 +2135,9 @@ struct pgn_ctx {
     DevBuf<uint8_t> ctcCodes{bufs};
     // pgn_crf_viterbi_rows_device: the backpointers of one group of rows (crf::row_scratch_bytes each), at most
     // crfCap bytes (pgn_ctx_set_crf_scratch); PGN_CRF_TRACEBACK=split moves the traceback into a kernel of its own,
-    // =none leaves it out (measurements only: no codes are written)
+    // =none leaves it out (measurements only: no codes are written).  pgn_crf_posterior_rows_device keeps its forward
+    // vectors (crf::post_row_scratch_bytes per row) in the same memory under the same cap: a call sequence of the
+    // context follows the one before it, so the two never hold it at once.
     DevBuf<uint32_t> crfBp{bufs};
     uint64_t crfCap = crf::kDefaultScratch;
     int crfTrace = 0;  // 0 in the row's workgroup, 1 split, 2 none
@@ -3822,6 +3826,111 @@ extern "C" int pgn_crf_viterbi_rows_device(pgn_ctx* c, const pgn_crf_params* par
             HIPCHK(hipGetLastError());
         }
     }
+    return PGN_OK;
+}
+
+// ---- posteriors of model rows (pgn_crf_post.h) and qualities of bases (pgn_qual.h) -----------------------
+template <uint32_t K, typename E, uint32_t TR>
+static void crf_post_launch_one(const crf::PostArgs& a, uint64_t nrows, hipStream_t s)
+{
+    hipLaunchKernelGGL((crf::crf_posterior_kernel<K, E, TR>), dim3((unsigned)nrows), dim3(crf::Shape<K, E, TR>::kThreads), 0,
+                       s, a);
+}
+template <uint32_t K>
+static void crf_post_launch_k(const crf::PostArgs& a, uint64_t nrows, bool f32, uint32_t tr, hipStream_t s)
+{
+    if (f32)
+        tr == 5 ? crf_post_launch_one<K, float, 5>(a, nrows, s) : crf_post_launch_one<K, float, 4>(a, nrows, s);
+    else
+        tr == 5 ? crf_post_launch_one<K, _Float16, 5>(a, nrows, s) : crf_post_launch_one<K, _Float16, 4>(a, nrows, s);
+}
+
+extern "C" int pgn_crf_posterior_rows_device(pgn_ctx* c, const pgn_crf_params* params, uint64_t nrows, uint32_t T,
+                                             const void* d_rows, uint64_t row_stride_bytes, uint64_t frame_stride_bytes,
+                                             float* d_post, uint64_t post_row_stride, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!crf::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if (T == 0 || T > crf::kMaxT) return PGN_ERR_INVALID_ARG;
+    const uint32_t elem = ctc::elem_bytes(params->score_type), S = crf::states(params->state_len);
+    const uint64_t frameBytes = (uint64_t)params->transitions * S * elem;
+    if (frame_stride_bytes < frameBytes && T != 1) return PGN_ERR_INVALID_ARG;
+    if ((uintptr_t)d_rows % elem || row_stride_bytes % elem || frame_stride_bytes % elem) return PGN_ERR_INVALID_ARG;
+    if (post_row_stride < 4ull * T && nrows > 1) return PGN_ERR_INVALID_ARG;
+    if ((uintptr_t)d_post % 4) return PGN_ERR_INVALID_ARG;
+    if (nrows >> 32) return PGN_ERR_INVALID_ARG;
+    if (nrows && (!d_rows || !d_post)) return PGN_ERR_INVALID_ARG;
+    const uint64_t rowBytes = crf::post_row_scratch_bytes(S, T);
+    uint64_t cap;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        cap = c->crfCap;
+    }
+    if (rowBytes > cap) return PGN_ERR_INVALID_ARG;
+    if (nrows == 0) return PGN_OK;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    const uint64_t groupRows = std::min<uint64_t>(cap / rowBytes, 1u << 30);
+    const int rc = reserve(c, {{c->crfBp, (size_t)(std::min(nrows, groupRows) * rowBytes)}});
+    if (rc != PGN_OK) return rc;
+    crf::PostArgs a{};
+    a.rowStride = row_stride_bytes;
+    a.frameStride = frame_stride_bytes;
+    a.T = T;
+    a.stay = params->stay_score;
+    a.postStride = post_row_stride;
+    a.fwd = static_cast<float*>(c->crfBp.p);
+    a.rowWords = rowBytes / 4;
+    // the groups follow each other on the stream, so each finds the scratch free
+    for (uint64_t g0 = 0; g0 < nrows; g0 += groupRows) {
+        const uint64_t n = std::min(groupRows, nrows - g0);
+        a.rows = static_cast<const uint8_t*>(d_rows) + g0 * row_stride_bytes;
+        a.post = d_post + g0 * post_row_stride;
+        const bool f32 = params->score_type == PGN_OUT_F32;
+        switch (params->state_len) {
+        case 1: crf_post_launch_k<1>(a, n, f32, params->transitions, s); break;
+        case 2: crf_post_launch_k<2>(a, n, f32, params->transitions, s); break;
+        case 3: crf_post_launch_k<3>(a, n, f32, params->transitions, s); break;
+        case 4: crf_post_launch_k<4>(a, n, f32, params->transitions, s); break;
+        default: crf_post_launch_k<5>(a, n, f32, params->transitions, s); break;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return PGN_OK;
+}
+
+extern "C" int pgn_base_qual_device(pgn_ctx* c, const pgn_qual_params* params, size_t nreads, const uint64_t* d_read_frames,
+                                    const uint8_t* d_codes, const float* d_post, uint64_t frame_base,
+                                    uint64_t frame_capacity, const uint64_t* d_read_bases, const uint32_t* d_base_frame,
+                                    const int32_t* d_read_status, uint8_t* d_qual, uint64_t base_capacity, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!qual::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32 || frame_capacity >> 40) return PGN_ERR_INVALID_ARG;
+    if ((uintptr_t)d_post % 4) return PGN_ERR_INVALID_ARG;
+    if (nreads && (!d_read_frames || !d_read_bases || !d_read_status)) return PGN_ERR_INVALID_ARG;
+    if (frame_capacity && (!d_codes || !d_post)) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && (!d_base_frame || !d_qual)) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    qual::Args a{};
+    a.nreads = nreads;
+    a.readFrames = d_read_frames;
+    a.codes = d_codes;
+    a.post = d_post;
+    a.frameBase = frame_base;
+    a.capacity = std::min(frame_capacity, UINT64_MAX - frame_base);  // no frame index wraps
+    a.readBases = d_read_bases;
+    a.baseFrame = d_base_frame;
+    a.status = d_read_status;
+    a.qual = d_qual;
+    a.baseCapacity = base_capacity;
+    a.prm = *params;
+    hipLaunchKernelGGL(qual::base_qual_kernel, dim3((unsigned)std::min<uint64_t>(nreads, 1u << 20)), dim3(qual::kThreads), 0,
+                       sc.s, a);
+    HIPCHK(hipGetLastError());
     return PGN_OK;
 }
 

@@ -329,3 +329,119 @@ def crf_viterbi_signal(scores, state_len, transitions=5, stay_score=0.0):
         if j:
             s = ((j - 1) * S + s) >> 2
     return codes, np.float32(m)
+
+
+# ---- posteriors and qualities (CRF) -----------------------------------------------------------------------------
+def _lse5(cand):
+    """log(sum(exp)) over the first axis of five candidates, the largest taken out first, in cand's dtype and in
+    the device's order of adds."""
+    m = cand.max(0)
+    e = np.exp(cand - m)
+    return m + np.log(((e[0] + e[1]) + (e[2] + e[3])) + e[4])
+
+
+def crf_posteriors_signal(scores, state_len, transitions=5, stay_score=0.0, dtype=np.float64):
+    """The posterior marginals of one row's ``[T, C]`` CRF scores on the host (include/pgnano_hip.h, "Posteriors
+    and qualities (CRF)"): a log-sum-exp forward-backward pass, all arithmetic in ``dtype``.  Returns ``[T, 4]``
+    of ``dtype``: ``post[t][b]`` is the probability that the newest base of the state after frame ``t`` is ``b``.
+    ``np.float64`` (the default) is the reference; ``np.float32`` is the renormalising float32 form whose error
+    is the yardstick :func:`~rawnanoporesignalcompression_amd.quality.crf_posteriors` is held to.  Both subtract
+    element 0 of the vector a step reads, which changes no marginal and keeps the vectors near zero."""
+    scores = np.asarray(scores)
+    if scores.ndim != 2:
+        raise ValueError("scores must be [T, C]")
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype must be float32 or float64")
+    prm = crf_params(state_len, transitions, scores.dtype, stay_score)
+    tr, k, S = prm.transitions, prm.state_len, 4 ** prm.state_len
+    T = scores.shape[0]
+    if scores.shape[1] != tr * S or not 1 <= T <= _native.PGN_CRF_MAX_FRAMES:
+        raise ValueError(f"scores must be [T, {tr * S}] with 1 <= T <= 2^24 (got {scores.shape})")
+    x = scores.astype(dt.type).reshape(T, S, tr)
+    u = np.arange(S)
+    pred = (np.arange(4)[:, None] * S + u[None, :]) >> 2                   # p(s, b) as [b, s]
+    succ = ((u[None, :] << 2) | np.arange(4)[:, None]) & (S - 1)           # c(u, n) as [n, u]
+    top = u >> (2 * k - 2)
+    stay = np.full(S, prm.stay_score, dt.type)
+    cand = np.empty((5, S), dt.type)
+    fwd = np.empty((T, S), dt.type)
+    a = np.zeros(S, dt.type)
+    for t in range(T):
+        a = a - a[0]
+        cand[0] = a + (x[t, :, 0] if tr == 5 else stay)
+        for b in range(4):
+            cand[1 + b] = a[pred[b]] + x[t, :, tr - 4 + b]
+        a = _lse5(cand)
+        fwd[t] = a
+    post = np.empty((T, 4), dt.type)
+    b_ = np.zeros(S, dt.type)
+    for t in range(T - 1, -1, -1):
+        w = fwd[t] + b_
+        e = np.exp(w - w.max())
+        cls = e.reshape(S // 4, 4).sum(0)
+        post[t] = cls / cls.sum()
+        b_ = b_ - b_[0]
+        cand[0] = b_ + (x[t, :, 0] if tr == 5 else stay)
+        for n in range(4):
+            cand[1 + n] = b_[succ[n]] + x[t, succ[n], tr - 4 + top]
+        b_ = _lse5(cand)
+    return post
+
+
+def qual_thresholds(q_scale=1.0, q_shift=0.0, q_min=1, q_max=50):
+    """The thresholds of :func:`base_qual_signal` for qualities ``q_min..q_max``: ``thr[j] = floor(2^32 *
+    10^(-((q_min + j + 0.5) - q_shift) / (10 * q_scale)))`` in float64, clamped to uint32, for ``j`` in ``0 ..
+    q_max - q_min - 1``.  ``thr[j]`` is the mean error (in units of 2^-32) at which ``q_shift + q_scale * (-10
+    log10 err)`` rounds up to ``q_min + j + 1``, so the quality lies in ``[q_min, q_max]``."""
+    q_min, q_max = int(q_min), int(q_max)
+    q_scale, q_shift = float(q_scale), float(q_shift)
+    if not (0 <= q_min <= q_max <= _native.PGN_QUAL_MAX and q_scale > 0):
+        raise ValueError(f"need 0 <= q_min <= q_max <= {_native.PGN_QUAL_MAX} and q_scale > 0")
+    j = np.arange(q_max - q_min, dtype=np.float64)
+    thr = np.floor(2.0 ** 32 * 10.0 ** (-((q_min + j + 0.5) - q_shift) / (10.0 * q_scale)))
+    return np.clip(thr, 0, 2.0 ** 32 - 1).astype(np.uint32)
+
+
+def qual_params(thresholds=None, q_min=1):
+    """``pgn_qual_params``: ``thresholds`` (non-increasing uint32 values, by default :func:`qual_thresholds` from
+    ``q_min`` to 50) and the quality ``q_min`` of a base that no threshold admits."""
+    q_min = int(q_min)
+    thr = qual_thresholds(q_min=q_min, q_max=max(q_min, 50)) if thresholds is None else np.asarray(thresholds)
+    if thr.ndim != 1 or (thr.size and (thr.min() < 0 or thr.max() > 0xFFFFFFFF)):
+        raise ValueError("thresholds must be a one-dimensional array of uint32 values")
+    thr = thr.astype(np.uint32)
+    if not (0 <= q_min and q_min + thr.size <= _native.PGN_QUAL_MAX):
+        raise ValueError(f"need q_min >= 0 and q_min + len(thresholds) <= {_native.PGN_QUAL_MAX}")
+    if (thr[1:] > thr[:-1]).any():
+        raise ValueError("thresholds must not increase")
+    p = _native.QualParams(q_min, thr.size)
+    p.thr[:thr.size] = thr.tolist()
+    return p
+
+
+def base_qual_signal(codes, post, base_frame, n_frames, thresholds, q_min):
+    """The phred characters of one read's bases on the host (include/pgnano_hip.h, the rule of
+    pgn_base_qual_device): ``codes`` uint8 and ``post`` float32 ``[frames, 4]`` per frame of the read,
+    ``base_frame`` the frame of each base (as :func:`collapse_codes_signal` returns it), ``n_frames`` the read's
+    frame count.  Base ``g`` owns the frames from its own to the next base's (the last to the read's end); with
+    ``c`` the code of its first frame masked with 3, a frame's error is the float32 sum of the three other
+    probabilities in the order ``c+1, c+2, c+3``, as an integer in units of 2^-32; ``U`` is their sum and
+    ``qual[g] = 33 + q_min + #{j : U <= thresholds[j] * n}``.  Returns uint8, one per base."""
+    codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+    post = np.asarray(post, dtype=np.float32).reshape(-1, 4)
+    at = np.asarray(base_frame).astype(np.int64).reshape(-1)
+    prm = qual_params(thresholds, q_min)
+    thr = [int(v) for v in prm.thr[:prm.nthresholds]]
+    ends = np.append(at[1:], int(n_frames))
+    out = np.empty(at.size, np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for g, (t0, t1) in enumerate(zip(at.tolist(), ends.tolist())):
+            c = int(codes[t0]) & 3
+            p = post[t0:t1]
+            err = (p[:, (c + 1) & 3] + p[:, (c + 2) & 3]) + p[:, (c + 3) & 3]            # float32 adds
+            scaled = np.clip(err, np.float32(0), np.float32(1)).astype(np.float64) * 2.0 ** 32
+            u = np.where(np.isnan(err), 2.0 ** 32 - 1, np.minimum(np.trunc(scaled), 2.0 ** 32 - 1)).astype(np.uint64)
+            U, n = sum(int(v) for v in u), t1 - t0
+            out[g] = 33 + prm.q_min + sum(1 for v in thr if U <= v * n)
+    return out
