@@ -205,6 +205,49 @@ int z1m_no_match_certificate(const uint8_t* src, size_t n)
     return ok;
 }
 
+// The level-1 search of the single-block frame src[0, n), n <= 128 KiB, from an empty table.
+// mode 0: fast_search_serial.  mode 1: the encoder's dispatch -- small_search_serial (zstd1_model.h)
+// for n <= kSmallSearchBytes, and the general search otherwise or when the small search's log
+// overflows.  Writes the first maxSeq (litLength, offset, mlBase) triples and
+//   info[0] 1 when the small search produced the result   info[1] 1 when its log overflowed
+//   info[2] nbSeq   info[3] last literal run   info[4], info[5] repeat offsets on exit
+//   info[6..14] the small search's rounds, log entries, keys flagged by the filter, flagged keys
+//               the log refuted, log scans, and SmallSearchInfo's refutedAbsent, shadowed, fpThenHit, repFirst
+// Returns nbSeq, or (size_t)-1 for a size out of range.
+size_t z1m_small_search(const uint8_t* src, size_t n, int mode, uint32_t* out3, size_t maxSeq, uint32_t* info)
+{
+    if (n < 7 || n > kMaxSrc) return (size_t)-1;
+    const Params p = level1_params(n);
+    Seq* seqs = (Seq*)malloc((n / 4 + 2) * sizeof(Seq));
+    size_t lastLL = 0, nb = (size_t)-1;
+    uint32_t rep[3] = {1, 4, 8};
+    for (int i = 0; i < 15; i++) info[i] = 0;
+    if (mode == 1 && n <= kSmallSearchBytes) {
+        SmallSearchWork* w = (SmallSearchWork*)malloc(sizeof(SmallSearchWork));
+        SmallSearchInfo si;
+        nb = small_search_serial(src, n, p, rep, seqs, &lastLL, *w, &si);
+        free(w);
+        info[0] = nb != (size_t)-1;
+        info[1] = nb == (size_t)-1;
+        info[6] = si.rounds; info[7] = si.logEntries; info[8] = si.flagged; info[9] = si.falsePositives; info[10] = si.scans;
+        info[11] = si.refutedAbsent; info[12] = si.shadowed; info[13] = si.fpThenHit; info[14] = si.repFirst;
+    }
+    if (nb == (size_t)-1) {
+        uint32_t* ht = (uint32_t*)calloc((size_t)1 << 15, 4);
+        rep[0] = 1; rep[1] = 4;
+        nb = fast_search_serial(src, 0, n, p, ht, rep, seqs, &lastLL);
+        free(ht);
+    }
+    info[2] = (uint32_t)nb; info[3] = (uint32_t)lastLL; info[4] = rep[0]; info[5] = rep[1];
+    for (size_t i = 0; i < nb && i < maxSeq; i++) {
+        out3[3 * i] = seqs[i].litLength; out3[3 * i + 1] = seqs[i].offset; out3[3 * i + 2] = seqs[i].mlBase;
+    }
+    free(seqs);
+    return nb;
+}
+unsigned z1m_small_search_bytes(void) { return kSmallSearchBytes; }
+unsigned z1m_small_search_log_cap(void) { return kSmallLogCap; }
+
 long z1m_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap)
 {
     DecWork* w = (DecWork*)malloc(sizeof(DecWork));

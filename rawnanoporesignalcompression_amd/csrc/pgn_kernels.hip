@@ -309,7 +309,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void en
     S.coop = nullptr;
     uint32_t epoch = a.epochs[blockIdx.x];  // table state: epoch tag | written extent << 8 (ht_next_epoch)
     PhaseProf P;
-    P.init(a.prof);
+    P.init(a.prof, a.prof);  // (the encode's search attribution: PhaseProf::ext)
     const size_t G = a.G, units = (size_t)a.nu * G;
     while (true) {
         uint32_t u = 0;
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(64 * kCoopEncWaves) void enc_zstd_coop_kernel(EncAr
     S.coop = cmd;
     uint32_t epoch = a.epochs[u];  // table state of slot u (ht_next_epoch)
     PhaseProf P;
-    P.init(a.prof);
+    P.init(a.prof, a.prof);  // (the encode's search attribution: PhaseProf::ext)
     const uint32_t n = a.sizes[g * kStreams + s];
     ht_next_epoch(S.ht, epoch, n);
     const uint8_t* src = a.streams + g * kChunkStreamBytes + (a.nu == 1 ? a.sizes[g * kStreams + 1] : stream_off(s));
@@ -1625,7 +1625,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void en
     uint8_t* fbuf = streams + chunk_stream_bytes(capN);
     uint32_t epoch = a.epochs[blockIdx.x];  // table state: epoch tag | written extent << 8 (ht_next_epoch)
     PhaseProf P;
-    P.init(a.prof);
+    P.init(a.prof, a.prof);  // (the encode's search attribution: PhaseProf::ext)
     while (true) {
         uint32_t u = 0;
         if (lane == 0) u = atomicAdd(a.queue, 1u);

@@ -239,23 +239,32 @@ __device__ inline void wave_fill(uint8_t* dst, uint8_t v, size_t n)
 // `_build/libpgnano_hip_prof.so`, selected with PGN_PHASE_PROFILE=1).  Shader-clock cycles
 // accumulate per phase; lane 0 adds them to a global buffer at kernel end.
 // ---------------------------------------------------------------------------------------------
+#ifdef PGN_PROFILE
+#define PGN_PROF(...) __VA_ARGS__  // code of the diagnostic build only
+#else
+#define PGN_PROF(...)
+#endif
 constexpr int kPhases = 16;
 constexpr int kCounters = 16;  // event counters (loop trip counts) after the phase cycles
 // profile buffer: [encode phases][decode phases][encode counters][decode counters], then the same
 // pair for dec_huf_kernel (phases at kHufProfOff, counters 2 kPhases further on)
 constexpr int kHufProfOff = 2 * (kPhases + kCounters);
 constexpr int kProfWords = kHufProfOff + 2 * (kPhases + kCounters);
+static_assert(kHufProfOff + 2 * kPhases <= kProfWords, "PhaseProf::ext's words lie inside the profile buffer");
 struct PhaseProf {
 #ifdef PGN_PROFILE
     uint64_t* out;
     uint64_t last;
     uint64_t acc[kPhases];
     uint64_t cnt[kCounters];
-    __device__ void init(uint64_t* o)
+    // extOut: the profile buffer's base, given by the encode kernels alone (the only users of ext)
+    __device__ void init(uint64_t* o, uint64_t* extBase = nullptr)
     {
         out = o;
+        extOut = o ? extBase : nullptr;
         for (int i = 0; i < kPhases; i++) acc[i] = 0;
         for (int i = 0; i < kCounters; i++) cnt[i] = 0;
+        for (int i = 0; i < kPhases; i++) extv[i] = 0;
         last = o ? __builtin_amdgcn_s_memtime() : 0;
     }
     __device__ __forceinline__ void mark(int phase)
@@ -271,18 +280,31 @@ struct PhaseProf {
     {
         if (out) cnt[k] += v;
     }
+    // further encode figures (the match search's attribution), flushed to the words of the profile
+    // buffer that dec_huf_kernel's half leaves unused: extOut[kHufProfOff + kPhases + k], k < kPhases,
+    // counted from the buffer's base whatever `out` is; an instance without that base keeps none
+    uint64_t* extOut;
+    uint64_t extv[kPhases];
+    __device__ __forceinline__ void ext(int k, uint64_t v)
+    {
+        if (extOut) extv[k] += v;
+    }
     __device__ void flush()
     {
         if (out && lane_id() == 0) {
+            if (extOut)
+                for (int i = 0; i < kPhases; i++)
+                    atomicAdd((unsigned long long*)&extOut[kHufProfOff + kPhases + i], (unsigned long long)extv[i]);
             for (int i = 0; i < kPhases; i++) atomicAdd((unsigned long long*)&out[i], (unsigned long long)acc[i]);
             for (int i = 0; i < kCounters; i++)
                 atomicAdd((unsigned long long*)&out[2 * kPhases + i], (unsigned long long)cnt[i]);
         }
     }
 #else
-    __device__ __forceinline__ void init(uint64_t*) {}
+    __device__ __forceinline__ void init(uint64_t*, uint64_t* = nullptr) {}
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void count(int, uint64_t = 1) {}
+    __device__ __forceinline__ void ext(int, uint64_t) {}
     __device__ __forceinline__ void flush() {}
 #endif
 };

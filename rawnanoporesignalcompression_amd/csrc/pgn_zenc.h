@@ -22,6 +22,7 @@ namespace pgn {
 
 constexpr int kWinWords = 392;  // 1024 symbols * 12 bits / 32 + carry words
 constexpr int kFiltSlots = 512;  // match-search round filter (64 lanes x 2 hashes)
+using z1::kSmallSearchBytes;  // a single-block frame of at most this many bytes is a "small block"
 
 // FSE compression table of the Huffman weight alphabet (<= 13 symbols, tableLog <= 6)
 struct WCTable {
@@ -287,8 +288,9 @@ __device__ __forceinline__ bool cert_insert(lds_u64* words, uint32_t x)
     return (old & m) == m;
 }
 static_assert((kCertWords & (kCertWords - 1)) == 0, "filter words: a power of two");
+// (certRounds: profile builds count the rounds)
 __device__ __noinline__ bool no_match_certificate(const uint8_t* __restrict__ src, uint32_t n, unsigned hlog, unsigned mls,
-                                                  uint32_t off1)
+                                                  uint32_t off1 PGN_PROF(, uint32_t* certRounds = nullptr))
 {
     const uint32_t lane = (uint32_t)lane_id();
     src = uni(src);
@@ -315,6 +317,9 @@ __device__ __noinline__ bool no_match_certificate(const uint8_t* __restrict__ sr
     loads(pk, v8, rw);
     for (uint32_t ci = 0;; ci += 64) {
         if (2 * (ci + 64) > kCertKeys) return false;  // too many keys: the exact search decides
+#ifdef PGN_PROFILE
+        if (certRounds) ++*certRounds;
+#endif
         uint64_t v8N = 0;
         uint32_t rwN = 0;
         loads(pkN, v8N, rwN);
@@ -337,6 +342,384 @@ __device__ __noinline__ bool no_match_certificate(const uint8_t* __restrict__ sr
     }
 }
 
+struct SearchOut {
+    uint32_t nbSeq, lastLL, rep0, rep1, rounds;
+    uint32_t candIters;  // profile builds: wave iterations of the same-slot loops
+    PGN_PROF(uint32_t certRounds, certCycles;)  // profile builds: the no-match certificate's rounds and shader cycles
+    PGN_PROF(uint32_t smallPath;)  // 1: the small-block search gave the result, 2: its log overflowed
+};
+
+// ---------------------------------------------------------------------------------------------
+// The search of a small single-block frame (n <= kSmallSearchBytes) on chip: zstd1_model.h
+// small_search_serial, by the wave.  The rounds are fast_search_wave's (below: 64 speculated visits,
+// the writes of a round's earlier visits seen through the round filter, the first hit by ballot,
+// the hit processed as the serial loop does), but the block lies in LDS and there is no hash table:
+// committed writes go, in the serial loop's order, to a log in LDS, and a visit's table candidate is
+// the latest log entry with its hash -- looked up, by a wave-wide backward scan, only for the
+// round's first visit whose key (hash, 4 bytes) a Bloom filter over the earlier rounds' keys does
+// not rule out.  A round whose first visit's repcode holds asks nothing of the table at all.  So a
+// round waits on LDS only, and nothing of the search reaches HBM but the sequences.  Returns
+// nbSeq = kSmallOverflow when the log is full: the caller then runs the general search from the
+// frame's start (the table untouched so far), so the bytes never differ.  DESIGN.md §5 has the
+// exactness argument.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSmallFiltSlots = 128;
+constexpr uint32_t kSmallBlkWords = z1::kSmallSearchBytes / 4 + 4;  // an aligned 12-byte read at the last byte stays inside
+constexpr uint32_t kSmallOverflow = 0xFFFFFFFFu;
+struct alignas(16) SmallLds {
+    uint64_t filt[kSmallFiltSlots];
+    uint32_t vh0[64], vh1[64], vpk[64], vd0[64], vd1[64];
+    uint64_t bloom[z1::kSmallBloomWords];
+    uint32_t log[z1::kSmallLogCap];
+    uint32_t blk[kSmallBlkWords];  // the block, zeros behind it
+};
+// like the certificate's filter, an overlay of the whole codec LDS: nothing of EncLds is live during the search
+static_assert(sizeof(SmallLds) <= kCodecLdsBytes, "small-block search LDS exceeds the codec LDS");
+static_assert(z1::kSmallSearchBytes + 1 < (1u << 16), "log entries hold the index in 16 bits");
+// ... and the hash above it: level1_params caps the hash log at the source's bit length + 1
+static_assert(z1::kSmallSearchBytes <= (1u << 15), "log entries hold the hash (hashLog <= 16) in 16 bits");
+#define sSmall (*reinterpret_cast<SmallLds*>(sCodecLds))
+// little-endian reads of the staged block at any byte position (aligned words, shifted)
+__device__ __forceinline__ uint32_t sblk_ld32(const SmallLds& L, int32_t p)
+{
+    const uint32_t w = (uint32_t)p >> 2, sh = 8u * ((uint32_t)p & 3u);
+    return (uint32_t)((((uint64_t)L.blk[w + 1] << 32) | L.blk[w]) >> sh);
+}
+__device__ __forceinline__ uint64_t sblk_ld64(const SmallLds& L, int32_t p)
+{
+    const uint32_t w = (uint32_t)p >> 2, sh = 8u * ((uint32_t)p & 3u);
+    const uint32_t a = L.blk[w], b = L.blk[w + 1], c = L.blk[w + 2];
+    const uint32_t lo = (uint32_t)((((uint64_t)b << 32) | a) >> sh), hi = (uint32_t)((((uint64_t)c << 32) | b) >> sh);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint32_t sblk_byte(const SmallLds& L, int32_t p)
+{
+    return (L.blk[(uint32_t)p >> 2] >> (8u * ((uint32_t)p & 3u))) & 0xFFu;
+}
+// wave_match_count / wave_back_count on the staged block
+__device__ inline uint32_t sblk_match_count(const SmallLds& L, uint32_t a, uint32_t b, uint32_t end)
+{
+    const uint32_t o = 4u * (uint32_t)lane_id();
+    uint32_t n = 0;
+    while (a + n < end) {
+        const uint32_t len = end - (a + n);
+        const uint32_t nv = len > o ? (len - o < 4u ? len - o : 4u) : 0u;  // my bytes inside the block
+        uint32_t x = 0;
+        if (nv) {
+            x = sblk_ld32(L, (int32_t)(a + n + o)) ^ sblk_ld32(L, (int32_t)(b + n + o));
+            if (nv < 4u) x &= (1u << (8u * nv)) - 1u;
+        }
+        const uint32_t mism = x ? o + ((uint32_t)__builtin_ctz(x) >> 3) : 0xFFFFFFFFu;
+        const uint64_t mm = ballot(mism != 0xFFFFFFFFu);
+        if (mm) return n + readlane_u32(mism, __builtin_ctzll(mm));
+        if (len <= 256u) return len + n;  // matched to the end
+        n += 256;
+    }
+    return n;
+}
+__device__ inline uint32_t sblk_back_count(const SmallLds& L, uint32_t a, uint32_t b, uint32_t lim)
+{
+    const uint32_t lane = (uint32_t)lane_id();
+    uint32_t n = 0;
+    while (n < lim) {
+        const uint32_t o = n + lane + 1;
+        const bool diff = (o <= lim) && sblk_byte(L, (int32_t)(a - o)) != sblk_byte(L, (int32_t)(b - o));
+        const uint64_t m = ballot(diff || o > lim);
+        if (m) return n + (uint32_t)__builtin_ctzll(m);
+        n += 64;
+    }
+    return lim;
+}
+// (the frame's first block: rep0 / rep1 are the frame's initial repeat offsets; the no-match
+// certificate is tried first, as in fast_search_wave -- a noise block would fill the log)
+__device__ __noinline__ SearchOut small_search_wave(const uint8_t* __restrict__ src, uint32_t n, unsigned hlog, unsigned mls,
+                                                    z1::Seq* __restrict__ seqs, uint32_t rep0, uint32_t rep1)
+{
+    SmallLds& L = sSmall;
+    const uint32_t lane = (uint32_t)lane_id();
+    src = uni(src);
+    n = uni(n);
+    hlog = uni(hlog);
+    mls = uni(mls);
+    seqs = uni(seqs);
+    uint32_t off1 = uni(rep0), off2 = uni(rep1), offSaved = 0;
+    if (off2 > 1) { offSaved = off2; off2 = 0; }  // beyond the window at the frame's first position (maxRep 1)
+    if (off1 > 1) { offSaved = off1; off1 = 0; }
+    const int32_t iend = (int32_t)n, ilimit = (int32_t)n - 8;
+    const uint32_t lowIdx = 1;  // a frame within its window
+    SearchOut r;
+    r.candIters = 0;
+    PGN_PROF(r.certRounds = 0;)
+    PGN_PROF(const uint64_t certT0 = __builtin_amdgcn_s_memtime();)
+#if !defined(PGN_NO_CERT) && !defined(PGN_SMALL_NO_CERT)  // A/B builds: small blocks straight into the exact search
+    const bool certified = no_match_certificate(src, n, hlog, mls, off1 PGN_PROF(, &r.certRounds));
+#else
+    const bool certified = false;
+#endif
+    PGN_PROF(r.certCycles = (uint32_t)(__builtin_amdgcn_s_memtime() - certT0);)
+    if (certified) {  // the whole frame is one literals block
+        r.nbSeq = 0;
+        r.lastLL = n;
+        r.rep0 = off1 ? off1 : offSaved;
+        r.rep1 = off2 ? off2 : offSaved;
+        r.rounds = 0;
+        PGN_PROF(r.smallPath = 0;)
+        return r;
+    }
+    PGN_PROF(r.smallPath = 2;)
+    r.nbSeq = kSmallOverflow;
+    r.lastLL = r.rep0 = r.rep1 = r.rounds = 0;
+    // the block into LDS (whole words from the stream; the last, partial one byte by byte), zeros behind it
+    for (uint32_t w = lane; w < (n + 3) / 4 + 4; w += 64) {  // <= kSmallBlkWords
+        uint32_t x = 0;
+        if (4 * w + 4 <= n) x = ld32u(src + 4 * w);
+        else
+            for (uint32_t b = 0; b < 4; b++)
+                if (4 * w + b < n) x |= (uint32_t)gb(src + 4 * w + b) << (8 * b);
+        L.blk[w] = x;
+    }
+    for (uint32_t i = lane; i < (uint32_t)kSmallFiltSlots; i += 64) L.filt[i] = 0;
+    for (uint32_t i = lane; i < z1::kSmallBloomWords; i += 64) L.bloom[i] = 0;
+    lds_sync();
+    uint32_t nbSeq = 0, rounds = 0, logN = 0;
+    const uint64_t below = (1ull << lane) - 1ull;
+    int32_t ip0 = 1, anchor = 0;
+    uint32_t chain = 1, ci = 0;  // kVisitChains: the frame's first position is 1
+    // one committed write outside the rounds' own (wave-uniform: scalar arithmetic): the position's
+    // hash and index into the log, its key into the filter
+    auto insert = [&](int32_t pos) {
+        const uint64_t w = uni(sblk_ld64(L, pos));
+        const uint32_t h = z1::hash_word(w, hlog, mls);
+        uint32_t bw;
+        const uint64_t bm = z1::small_bloom_bits(h, (uint32_t)w, &bw);
+        if (lane == 0) {
+            L.log[logN] = (h << 16) | ((uint32_t)pos + 1);
+            L.bloom[bw] |= bm;
+        }
+        logN++;
+    };
+    while (ip0 + 1 < ilimit) {
+        rounds++;
+        const uint32_t* E = kVisitChains.e[chain];
+        const int32_t pk = (int32_t)E[ci + lane] + (anchor - 256), pNext = (int32_t)E[ci + 64] + (anchor - 256);
+        const bool valid = (pk + 1 < ilimit);
+        uint64_t v8 = 0;
+        uint32_t repw = 0;
+        if (valid) {
+            v8 = sblk_ld64(L, pk);
+            repw = (off1 > 0) ? sblk_ld32(L, pk + 2 - (int32_t)off1) : 0u;
+        }
+        const bool rep = valid && (off1 > 0) && (repw == (uint32_t)(v8 >> 16));
+        const uint64_t repb = ballot(rep);
+        int f = 64;
+        bool repf = false, c0f = false;
+        uint32_t m0f = 0, m1f = 0, fwdKnown = 0;
+        if (repb & 1) {
+            // The repcode of the round's first visit decides the round before anything is asked of the
+            // table: only that visit's two writes are committed, nothing is speculated (most rounds of
+            // a stream of long runs, such as C5's Lhigh, end here).
+            if (logN + 2 > z1::kSmallLogCap) return r;
+            insert(ip0);
+            insert(ip0 + 1);
+            f = 0;
+            repf = true;
+        } else {
+        uint32_t h0 = 0xFFFFFFFFu, h1 = 0xFFFFFFFEu;
+        uint64_t M0 = 0, M1 = 0, bm0 = 0, bm1 = 0;
+        uint32_t bw0 = 0, bw1 = 0;
+        bool maybe0 = false, maybe1 = false;
+        if (valid) {
+            h0 = z1::hash_word(v8, hlog, mls);
+            h1 = z1::hash_word(v8 >> 8, hlog, mls);
+            // the filter holds the keys of the rounds before this one (and of the tails between them)
+            bm0 = z1::small_bloom_bits(h0, (uint32_t)v8, &bw0);
+            bm1 = z1::small_bloom_bits(h1, (uint32_t)(v8 >> 8), &bw1);
+            maybe0 = (L.bloom[bw0] & bm0) == bm0;
+            maybe1 = (L.bloom[bw1] & bm1) == bm1;
+            atomicOr((unsigned long long*)&L.filt[h0 & (kSmallFiltSlots - 1)], (unsigned long long)(1ull << lane));
+            atomicOr((unsigned long long*)&L.filt[h1 & (kSmallFiltSlots - 1)], (unsigned long long)(1ull << lane));
+        }
+        L.vh0[lane] = h0;
+        L.vh1[lane] = h1;
+        L.vpk[lane] = (uint32_t)pk;
+        L.vd0[lane] = (uint32_t)v8;
+        L.vd1[lane] = (uint32_t)(v8 >> 8);
+        lds_sync();
+        if (valid) {
+            M0 = L.filt[h0 & (kSmallFiltSlots - 1)];
+            M1 = L.filt[h1 & (kSmallFiltSlots - 1)];
+            // this round's keys, the visits speculated past its hit included (false positives only)
+            atomicOr((unsigned long long*)&L.bloom[bw0], (unsigned long long)bm0);
+            atomicOr((unsigned long long*)&L.bloom[bw1], (unsigned long long)bm1);
+        }
+        lds_sync();
+        if (valid) {
+            L.filt[h0 & (kSmallFiltSlots - 1)] = 0;
+            L.filt[h1 & (kSmallFiltSlots - 1)] = 0;
+        }
+        // the latest write of an earlier visit of this round to my slots (its bytes known exactly)
+        uint32_t m0 = 0, m1 = 0, d0 = 0, d1 = 0;
+        bool fw0 = false, fw1 = false;
+        for (uint64_t cand = M0 & below; cand;) {
+            const int jj = 63 - __builtin_clzll(cand);
+            const uint32_t pj = L.vpk[jj];
+            if (L.vh1[jj] == h0) { m0 = pj + 2; d0 = L.vd1[jj]; fw0 = true; break; }
+            if (L.vh0[jj] == h0) { m0 = pj + 1; d0 = L.vd0[jj]; fw0 = true; break; }
+            cand &= ~(1ull << jj);
+        }
+        for (uint64_t cand = M1 & below; cand;) {
+            const int jj = 63 - __builtin_clzll(cand);
+            const uint32_t pj = L.vpk[jj];
+            if (L.vh1[jj] == h1) { m1 = pj + 2; d1 = L.vd1[jj]; fw1 = true; break; }
+            if (L.vh0[jj] == h1) { m1 = pj + 1; d1 = L.vd0[jj]; fw1 = true; break; }
+            cand &= ~(1ull << jj);
+        }
+        bool c0 = false, c1 = false;
+        if (valid) {
+            c0 = fw0 ? (m0 > lowIdx && d0 == (uint32_t)v8) : maybe0;
+            c1 = fw1 ? (m1 > lowIdx && d1 == (uint32_t)(v8 >> 8)) : maybe1;
+        }
+        // The first hit decides the round.  A key the filter flagged is resolved against the log: the
+        // latest entry with its hash is the table's entry, and counting the match forward from its
+        // first byte compares the 4 bytes; a flagged key the log refutes is dropped and the next hit taken.
+        uint64_t hits = ballot(rep || c0 || c1);
+        {
+            const uint64_t fwb0 = ballot(fw0), fwb1 = ballot(fw1);
+            while (hits) {
+                const int ff = __builtin_ctzll(hits);
+                if ((repb >> ff) & 1) break;
+                const bool isC0 = (ballot(c0) >> ff) & 1;
+                if (((isC0 ? fwb0 : fwb1) >> ff) & 1) break;  // an earlier visit's write: bytes compared exactly
+                const uint32_t hq = readlane_u32(isC0 ? h0 : h1, ff);
+                uint32_t mf = 0;
+                for (int32_t base = (int32_t)logN; base > 0; base -= 64) {  // lane 0 reads the latest entry
+                    const int32_t i = base - 1 - (int32_t)lane;
+                    const uint32_t e = i >= 0 ? L.log[i] : 0u;
+                    const uint64_t mm = ballot(i >= 0 && (e >> 16) == hq);
+                    if (mm) {
+                        mf = readlane_u32(e, __builtin_ctzll(mm)) & 0xFFFFu;
+                        break;
+                    }
+                }
+                const uint32_t ipc = readlane_u32((uint32_t)pk, ff) + (isC0 ? 0u : 1u);
+                const uint32_t nm = mf > lowIdx ? sblk_match_count(L, ipc, mf - 1, (uint32_t)iend) : 0u;
+                if (nm >= 4) {
+                    if ((int)lane == ff) {
+                        if (isC0) m0 = mf;
+                        else m1 = mf;
+                    }
+                    fwdKnown = nm;
+                    break;
+                }
+                if ((int)lane == ff) {
+                    if (isC0) c0 = false;
+                    else c1 = false;
+                }
+                hits = ballot(rep || c0 || c1);
+            }
+        }
+        const uint64_t vmask = ballot(valid);
+        f = hits ? __builtin_ctzll(hits) : 64;
+        const int lastCommit = hits ? f : (63 - __builtin_clzll(vmask));
+        {
+            // the committed visits' writes, in the serial loop's order: ip0's then ip1's, visit by visit
+            const uint64_t cm = ballot(valid && (int)lane <= lastCommit);
+            const uint32_t cnt = 2u * (uint32_t)__builtin_popcountll(cm);
+            if (logN + cnt > z1::kSmallLogCap) return r;
+            if ((cm >> lane) & 1) {
+                const uint32_t at = logN + 2u * mbcnt(cm);
+                L.log[at] = (h0 << 16) | ((uint32_t)pk + 1);
+                L.log[at + 1] = (h1 << 16) | ((uint32_t)pk + 2);
+            }
+            logN += cnt;
+        }
+        lds_sync();
+        if (!hits) {
+            if (vmask == ~0ull) {
+                ip0 = pNext;
+                ci += 64;
+                continue;
+            }
+            break;
+        }
+        repf = (repb >> f) & 1;
+        c0f = (ballot(c0) >> f) & 1;
+        m0f = readlane_u32(m0, f);
+        m1f = readlane_u32(m1, f);
+        }
+        // the match found at visit f, processed exactly as the serial loop does
+        const int32_t ipf = (int32_t)readlane_u32((uint32_t)pk, f);
+        const uint32_t cur0 = (uint32_t)ipf + 1;
+        int32_t ipm, match0;
+        uint32_t mLength, offcode;
+        if (repf) {
+            const int32_t ip2 = ipf + 2;
+            mLength = (sblk_byte(L, ip2 - 1) == sblk_byte(L, ip2 - (int32_t)off1 - 1)) ? 1u : 0u;
+            ipm = ip2 - (int32_t)mLength;
+            match0 = ipm - (int32_t)off1;
+            mLength += 4;
+            offcode = 0;
+        } else {
+            if (c0f) { ipm = ipf; match0 = (int32_t)m0f - 1; }
+            else { ipm = ipf + 1; match0 = (int32_t)m1f - 1; }
+            off2 = off1;
+            off1 = (uint32_t)(ipm - match0);
+            offcode = off1 + 2;
+            mLength = 4;
+            const int32_t lim = (ipm - anchor) < match0 ? (ipm - anchor) : match0;  // down to the anchor or position 0
+            const uint32_t back = lim > 0 ? sblk_back_count(L, (uint32_t)ipm, (uint32_t)match0, (uint32_t)lim) : 0u;
+            ipm -= (int32_t)back;
+            match0 -= (int32_t)back;
+            mLength += back;
+        }
+        // (the forward part starts 4 bytes past the candidate, whatever the backward extension)
+        mLength += fwdKnown ? fwdKnown - 4u
+                            : sblk_match_count(L, (uint32_t)ipm + mLength, (uint32_t)match0 + mLength, (uint32_t)iend);
+        if (lane == 0) {
+            seqs[nbSeq].litLength = (uint32_t)(ipm - anchor);
+            seqs[nbSeq].offset = offcode + 1;
+            seqs[nbSeq].mlBase = mLength - 3;
+        }
+        nbSeq++;
+        ip0 = ipm + (int32_t)mLength;
+        anchor = ip0;
+        chain = 0;
+        ci = 0;
+        if (ip0 <= ilimit) {
+            // the writes after a match
+            if (logN + 2 > z1::kSmallLogCap) return r;
+            insert((int32_t)cur0 + 1);
+            insert(ip0 - 2);
+            if (off2 > 0) {
+                while ((ip0 <= ilimit) && sblk_ld32(L, ip0) == sblk_ld32(L, ip0 - (int32_t)off2)) {
+                    const uint32_t rLength = sblk_match_count(L, (uint32_t)ip0 + 4, (uint32_t)ip0 + 4 - off2, (uint32_t)iend) + 4;
+                    const uint32_t t = off2;
+                    off2 = off1;
+                    off1 = t;
+                    if (logN + 1 > z1::kSmallLogCap) return r;
+                    insert(ip0);
+                    if (lane == 0) {
+                        seqs[nbSeq].litLength = 0;
+                        seqs[nbSeq].offset = 1;
+                        seqs[nbSeq].mlBase = rLength - 3;
+                    }
+                    nbSeq++;
+                    ip0 += (int32_t)rLength;
+                    anchor = ip0;
+                }
+            }
+        }
+        lds_sync();
+    }
+    PGN_PROF(r.smallPath = 1;)
+    r.nbSeq = nbSeq;
+    r.lastLL = (uint32_t)(iend - anchor);
+    r.rep0 = off1 ? off1 : offSaved;
+    r.rep1 = off2 ? off2 : offSaved;
+    r.rounds = rounds;
+    return r;
+}
+
 // Match search (ZSTD_compressBlock_fast, libzstd 1.4.x) speculated over 64 consecutive visits.
 // The visit positions follow a data-independent recurrence until a match is found, so lane k takes
 // visit k of the round: it hashes its two positions, reads the table (entries (tag << 17) | idx,
@@ -346,11 +729,9 @@ __device__ __noinline__ bool no_match_certificate(const uint8_t* __restrict__ sr
 // the next round starts after it.  Same-slot writers inside a round are found through an LDS filter
 // (one bit per lane per slot), checked exactly only for the lanes whose filter slots collide.
 // Searches the block [start, end) of src (table and positions frame-wide, zstd1_model.h
-// fast_search_serial); rep0 / rep1 are the confirmed repeat offsets on entry.
-struct SearchOut {
-    uint32_t nbSeq, lastLL, rep0, rep1, rounds;
-    uint32_t candIters;  // profile builds: wave iterations of the same-slot loops
-};
+// fast_search_serial); rep0 / rep1 are the confirmed repeat offsets on entry.  A single-block frame
+// (`single`) first tries the no-match certificate.  (zstd1_compress_wave sends a small single-block
+// frame to small_search_wave above first, and comes here when that search's log overflowed.)
 __device__ __noinline__ SearchOut fast_search_wave(const uint8_t* __restrict__ src, uint32_t start, uint32_t end, unsigned hlog,
                                                    unsigned mls, uint32_t* __restrict__ ht, uint32_t tag,
                                                    z1::Seq* __restrict__ seqs, uint32_t rep0, uint32_t rep1, uint32_t idxBits,
@@ -387,14 +768,25 @@ __device__ __noinline__ SearchOut fast_search_wave(const uint8_t* __restrict__ s
 #ifdef PGN_NO_CERT  // A/B builds: the exact search only
     single = false;
 #endif
-    if (single && no_match_certificate(src, end, hlog, mls, off1)) {  // the whole frame is one literals block
+#ifdef PGN_PROFILE
+    uint32_t certRounds = 0;
+    const uint64_t certT0 = __builtin_amdgcn_s_memtime();
+    const bool certified = single && no_match_certificate(src, end, hlog, mls, off1, &certRounds);
+    const uint32_t certCycles = (uint32_t)(__builtin_amdgcn_s_memtime() - certT0);
+#else
+    const bool certified = single && no_match_certificate(src, end, hlog, mls, off1);
+#endif
+    if (certified) {  // the whole frame is one literals block
         SearchOut r;
+        PGN_PROF(r.certRounds = certRounds;)
+        PGN_PROF(r.certCycles = certCycles;)
         r.nbSeq = 0;
         r.lastLL = end - start;
         r.rep0 = off1 ? off1 : offSaved;
         r.rep1 = off2 ? off2 : offSaved;
         r.rounds = 0;
         r.candIters = 0;
+        PGN_PROF(r.smallPath = 0;)
         return r;
     }
     uint32_t nbSeq = 0, rounds = 0, candIters = 0;
@@ -656,6 +1048,9 @@ __device__ __noinline__ SearchOut fast_search_wave(const uint8_t* __restrict__ s
     r.rep1 = off2 ? off2 : offSaved;
     r.rounds = rounds;
     r.candIters = candIters;
+    PGN_PROF(r.certRounds = certRounds;)
+    PGN_PROF(r.certCycles = certCycles;)
+    PGN_PROF(r.smallPath = 0;)
     return r;
 }
 
@@ -2185,10 +2580,38 @@ __device__ __noinline__ size_t zstd1_compress_wave(uint8_t* __restrict__ dst, co
         if (bs >= 7) {
 #endif
             const uint32_t ip0 = start + (start == 0 ? 1u : 0u);
-            const SearchOut so = fast_search_wave(src, start, start + bs, p.hashLog, p.mls, S.ht, tag, S.seqs, rep0, rep1,
-                                                  ht_idx_bits(n), z1::window_low_index(start + bs, p.windowLog),
-                                                  ip0 + 1u - z1::window_low_index(ip0, p.windowLog), first && last);
+            // a small single-block frame is searched on chip; when that search's log overflows, and
+            // everywhere else, the general search (which starts from the frame's table as it was)
+            SearchOut so;
+            so.nbSeq = kSmallOverflow;
+            bool again = false;  // the small search ran and its log overflowed
+#ifndef PGN_NO_SMALL_SEARCH  // A/B builds: the general search only
+            if (first && last && bs <= kSmallSearchBytes) {
+                so = small_search_wave(src, bs, p.hashLog, p.mls, S.seqs, rep0, rep1);
+                again = true;
+            }
+#endif
+            if (uni(so.nbSeq) == kSmallOverflow) {
+                // (after an overflow the certificate is known to have failed: not tried again)
+                so = fast_search_wave(src, start, start + bs, p.hashLog, p.mls, S.ht, tag, S.seqs, rep0, rep1, ht_idx_bits(n),
+                                      z1::window_low_index(start + bs, p.windowLog),
+                                      ip0 + 1u - z1::window_low_index(ip0, p.windowLog), first && last && !again);
+                PGN_PROF(if (again) so.smallPath = 2;)
+            }
             const uint32_t nbSeq = uni(so.nbSeq), lastLL = uni(so.lastLL);
+#ifdef PGN_PROFILE
+            if (P.out) {  // the search phase by kind: [0..5] small single-block frames, [6..11] every other block
+                const int k = (first && last && bs <= kSmallSearchBytes) ? 0 : 6;
+                P.ext(k + 5, __builtin_amdgcn_s_memtime() - P.last);  // the phase's wave-cycles
+                P.ext(k, 1);                       // blocks
+                P.ext(k + 1, uni(so.certRounds));  // certificate rounds
+                P.ext(k + 2, uni(so.certCycles));  //             wave-cycles (the rest of the phase is the exact search's)
+                P.ext(k + 3, uni(so.rounds));      // exact rounds
+                P.ext(k + 4, uni(so.rounds) ? 1 : 0);  // blocks that ran the exact search
+                P.ext(12, uni(so.smallPath) == 1 ? 1 : 0);  // searched on chip (small_search_wave)
+                P.ext(13, uni(so.smallPath) == 2 ? 1 : 0);  // its log overflowed: searched again by the general path
+            }
+#endif
             P.mark(1);
             P.count(0, uni(so.rounds));
             P.count(14, uni(so.candIters));

@@ -125,6 +125,255 @@ PGN_HD size_t fast_search_serial(const uint8_t* src, size_t start, size_t end, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// The same search for a small single-block frame (start 0, n <= kSmallSearchBytes) without a hash
+// table: the model of an on-chip search, in the wave search's rounds of 64 speculated visits
+// (pgn_zenc.h fast_search_wave).
+//   * Committed table writes are appended, in the serial loop's order, to a log of (hash, index);
+//     "the table's entry for hash h" is the latest log entry with hash h.
+//   * A visit asks the log only when a blocked Bloom filter over the keys (hash, first 4 bytes) of
+//     earlier rounds says that an equal key may have been written.  A key the filter calls absent
+//     cannot match: the table's entry for its hash, whatever it is, then holds other 4 bytes.  The
+//     filter is tested before the round's own keys go in (all 64 visits', also those speculated
+//     past the round's hit: they only add false positives; the log takes committed writes only).
+//   * Inside a round, a visit sees the writes of the visits before it exactly (their hashes and
+//     bytes are at hand), as the wave search does.
+//   * Only the round's first hit is resolved: a flagged key whose latest log entry does not match 4
+//     bytes is dropped and the next hit taken.
+//   * A round whose first visit's repcode holds is decided at once: that visit's two writes are
+//     committed, nothing else is hashed, asked or speculated.
+// Returns nbSeq, or (size_t)-1 when the log overflows (the caller then runs the general search from
+// the start: the bytes never differ).
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kSmallSearchBytes = 2048;
+constexpr uint32_t kSmallLogCap = 688;      // log entries: hash << 16 | index (position + 1); what the codec LDS leaves
+constexpr uint32_t kSmallBloomWords = 128;  // 64-bit filter words
+struct SmallSearchWork {
+    uint32_t log[kSmallLogCap];
+    uint64_t bloom[kSmallBloomWords];
+};
+struct SmallSearchInfo {
+    uint32_t rounds, logEntries, flagged, falsePositives, scans;
+    uint32_t refutedAbsent;  // flagged keys whose hash the log does not hold (a visit speculated past a hit left the key)
+    uint32_t shadowed;       // flagged keys refuted by a later entry of their hash, an older entry holding their 4 bytes
+    uint32_t fpThenHit;      // rounds that dropped a flagged key and then found their match
+    uint32_t repFirst;       // rounds decided by the repcode of their first visit
+};
+PGN_HD uint32_t small_fmix32(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+// the filter word and the four bits of the key (hash h, 4 bytes v): one mix, 31 of its bits (a block
+// holds a few hundred keys in 128 words, so four bits of a word keep false positives near 1 in 10^4)
+PGN_HD uint64_t small_bloom_bits(uint32_t h, uint32_t v, uint32_t* word)
+{
+    const uint32_t a = small_fmix32(v ^ (h * 0x9E3779B1u));
+    *word = (a >> 24) & (kSmallBloomWords - 1u);
+    return (1ull << (a & 63u)) | (1ull << ((a >> 6) & 63u)) | (1ull << ((a >> 12) & 63u)) | (1ull << ((a >> 18) & 63u));
+}
+PGN_HD size_t small_search_serial(const uint8_t* src, size_t n, const Params& p, uint32_t rep[3], Seq* seqs, size_t* lastLL,
+                                  SmallSearchWork& W, SmallSearchInfo* info)
+{
+    const unsigned hlog = p.hashLog, mls = p.mls;
+    const long iend = (long)n, ilimit = (long)n - 8;
+    const uint32_t lowIdx = 1;  // a frame within its window
+    size_t nbSeq = 0;
+    long anchor = 0;
+    uint32_t off1 = rep[0], off2 = rep[1], offSaved = 0;
+    if (off2 > 1) { offSaved = off2; off2 = 0; }  // maxRep at the frame's first position is 1
+    if (off1 > 1) { offSaved = off1; off1 = 0; }
+    uint32_t logN = 0;
+    for (uint32_t i = 0; i < kSmallBloomWords; i++) W.bloom[i] = 0;
+    SmallSearchInfo I = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    bool overflow = false;
+    auto bloom_add = [&](uint32_t h, uint32_t v) {
+        uint32_t w;
+        const uint64_t m = small_bloom_bits(h, v, &w);
+        W.bloom[w] |= m;
+    };
+    auto bloom_has = [&](uint32_t h, uint32_t v) {
+        uint32_t w;
+        const uint64_t m = small_bloom_bits(h, v, &w);
+        return (W.bloom[w] & m) == m;
+    };
+    auto log_add = [&](uint32_t h, uint32_t idx) {
+        if (logN >= kSmallLogCap) { overflow = true; return; }
+        W.log[logN++] = (h << 16) | idx;
+    };
+    auto log_latest = [&](uint32_t h) -> uint32_t {  // the index, 0 if the hash was never written
+        for (uint32_t i = logN; i > 0; i--)
+            if ((W.log[i - 1] >> 16) == h) return W.log[i - 1] & 0xFFFFu;
+        return 0;
+    };
+    uint32_t e0 = 257;  // the round's first visit: e = ip0 - anchor + 256 (257: the frame's first position is 1)
+    long ip0 = 1;
+    while (ip0 + 1 < ilimit && !overflow) {
+        I.rounds++;
+        long pk[64];
+        uint32_t h0[64], h1[64], v0[64], v1[64], m0[64], m1[64];
+        bool valid[64], repk[64], c0[64], c1[64], fw0[64], fw1[64];
+        uint32_t e = e0;
+        int nValid = 0;
+        for (int k = 0; k < 64; k++) {
+            pk[k] = (long)e - 256 + anchor;
+            e += e >> 7;
+            valid[k] = pk[k] + 1 < ilimit;
+            repk[k] = c0[k] = c1[k] = fw0[k] = fw1[k] = false;
+            m0[k] = m1[k] = 0;
+            if (!valid[k]) continue;
+            nValid = k + 1;
+            const uint64_t v8 = rd64(src + pk[k]);
+            h0[k] = hash_word(v8, hlog, mls);
+            h1[k] = hash_word(v8 >> 8, hlog, mls);
+            v0[k] = (uint32_t)v8;
+            v1[k] = (uint32_t)(v8 >> 8);
+            repk[k] = off1 > 0 && rd32(src + pk[k] + 2 - (long)off1) == (uint32_t)(v8 >> 16);
+            // the repcode of the round's first visit decides the round before anything is asked of the
+            // table: only that visit's two writes are committed, and nothing is speculated
+            if (k == 0 && repk[0]) {
+                I.repFirst++;
+                break;
+            }
+            // the latest write of an earlier visit of this round to my slots (ip1's after ip0's)
+            uint32_t d0 = 0, d1 = 0;
+            for (int j = k - 1; j >= 0 && !fw0[k]; j--) {
+                if (h1[j] == h0[k]) { m0[k] = (uint32_t)pk[j] + 2; d0 = v1[j]; fw0[k] = true; }
+                else if (h0[j] == h0[k]) { m0[k] = (uint32_t)pk[j] + 1; d0 = v0[j]; fw0[k] = true; }
+            }
+            for (int j = k - 1; j >= 0 && !fw1[k]; j--) {
+                if (h1[j] == h1[k]) { m1[k] = (uint32_t)pk[j] + 2; d1 = v1[j]; fw1[k] = true; }
+                else if (h0[j] == h1[k]) { m1[k] = (uint32_t)pk[j] + 1; d1 = v0[j]; fw1[k] = true; }
+            }
+            // (visits run to pk + 1 < ilimit in order, so every valid visit has its predecessors valid)
+            c0[k] = fw0[k] ? (m0[k] > lowIdx && d0 == v0[k]) : bloom_has(h0[k], v0[k]);
+            c1[k] = fw1[k] ? (m1[k] > lowIdx && d1 == v1[k]) : bloom_has(h1[k], v1[k]);
+            if (!fw0[k] && c0[k]) I.flagged++;
+            if (!fw1[k] && c1[k]) I.flagged++;
+        }
+        for (int k = 0; k < nValid; k++) {  // the round's keys, speculated ones included
+            bloom_add(h0[k], v0[k]);
+            bloom_add(h1[k], v1[k]);
+        }
+        // the first hit, a flagged key resolved against the log
+        int f = 64;
+        uint32_t fwdKnown = 0;
+        bool dropped = false;
+        for (int k = 0; k < nValid && f == 64; k++) {
+            while (repk[k] || c0[k] || c1[k]) {
+                if (repk[k]) { f = k; break; }
+                const bool isC0 = c0[k];
+                if (isC0 ? fw0[k] : fw1[k]) { f = k; break; }
+                I.scans++;
+                const uint32_t mf = log_latest(isC0 ? h0[k] : h1[k]);
+                const size_t nm = mf > lowIdx ? match_count(src, (size_t)pk[k] + (isC0 ? 0 : 1), mf - 1, (size_t)iend) : 0;
+                if (nm >= 4) {
+                    (isC0 ? m0[k] : m1[k]) = mf;
+                    fwdKnown = (uint32_t)nm;
+                    f = k;
+                    break;
+                }
+                I.falsePositives++;
+                dropped = true;
+                if (mf == 0) I.refutedAbsent++;
+                else {
+                    const uint32_t hq = isC0 ? h0[k] : h1[k], vq = isC0 ? v0[k] : v1[k];
+                    bool older = false;
+                    for (uint32_t i = 0; i < logN; i++)
+                        if ((W.log[i] >> 16) == hq && rd32(src + (W.log[i] & 0xFFFFu) - 1) == vq) older = true;
+                    if (older) I.shadowed++;
+                }
+                if (isC0) c0[k] = false;
+                else c1[k] = false;
+            }
+        }
+        if (dropped && f < 64) I.fpThenHit++;
+        const int lastCommit = f < 64 ? f : nValid - 1;
+        for (int k = 0; k <= lastCommit; k++) {
+            log_add(h0[k], (uint32_t)pk[k] + 1);
+            log_add(h1[k], (uint32_t)pk[k] + 2);
+        }
+        if (overflow) break;
+        if (f == 64) {
+            if (nValid < 64) break;
+            ip0 = (long)e - 256 + anchor;
+            e0 = e;
+            continue;
+        }
+        // the match at visit f, as the serial loop processes it
+        const long ipf = pk[f];
+        const uint32_t cur0 = (uint32_t)ipf + 1;
+        long ipm, match0;
+        size_t mLength;
+        uint32_t offcode;
+        if (repk[f]) {
+            const long ip2 = ipf + 2;
+            mLength = (src[ip2 - 1] == src[ip2 - (long)off1 - 1]) ? 1 : 0;
+            ipm = ip2 - (long)mLength;
+            match0 = ipm - (long)off1;
+            mLength += 4;
+            offcode = 0;
+        } else {
+            if (c0[f]) { ipm = ipf; match0 = (long)m0[f] - 1; }
+            else { ipm = ipf + 1; match0 = (long)m1[f] - 1; }
+            off2 = off1;
+            off1 = (uint32_t)(ipm - match0);
+            offcode = off1 + 2;
+            mLength = 4;
+            while (ipm > anchor && match0 > 0 && src[ipm - 1] == src[match0 - 1]) {
+                ipm--;
+                match0--;
+                mLength++;
+            }
+        }
+        // (the forward part starts 4 bytes past the candidate, whatever the backward extension)
+        mLength += fwdKnown ? fwdKnown - 4 : match_count(src, (size_t)ipm + mLength, (size_t)match0 + mLength, (size_t)iend);
+        seqs[nbSeq].litLength = (uint32_t)(ipm - anchor);
+        seqs[nbSeq].offset = offcode + 1;
+        seqs[nbSeq].mlBase = (uint32_t)(mLength - 3);
+        nbSeq++;
+        ip0 = ipm + (long)mLength;
+        anchor = ip0;
+        e0 = 256;
+        if (ip0 <= ilimit) {
+            auto insert = [&](long pos) {
+                const uint64_t w = rd64(src + pos);
+                const uint32_t h = hash_word(w, hlog, mls);
+                log_add(h, (uint32_t)pos + 1);
+                bloom_add(h, (uint32_t)w);
+            };
+            insert((long)cur0 + 1);
+            insert(ip0 - 2);
+            if (off2 > 0) {
+                while (ip0 <= ilimit && rd32(src + ip0) == rd32(src + ip0 - (long)off2)) {
+                    const size_t rLength = match_count(src, (size_t)ip0 + 4, (size_t)ip0 + 4 - off2, (size_t)iend) + 4;
+                    const uint32_t t = off2;
+                    off2 = off1;
+                    off1 = t;
+                    insert(ip0);
+                    ip0 += (long)rLength;
+                    seqs[nbSeq].litLength = 0;
+                    seqs[nbSeq].offset = 1;
+                    seqs[nbSeq].mlBase = (uint32_t)(rLength - 3);
+                    nbSeq++;
+                    anchor = ip0;
+                }
+            }
+        }
+    }
+    I.logEntries = logN;
+    if (info) *info = I;
+    if (overflow) return (size_t)-1;
+    rep[0] = off1 ? off1 : offSaved;
+    rep[1] = off2 ? off2 : offSaved;
+    *lastLL = (size_t)(iend - anchor);
+    return nbSeq;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Literals section (ZSTD_compressLiterals -> HUF_compress{1,4}X_repeat).  `prev` is the Huffman
 // table state the frame carries from its last compressed block (HUF_repeat_none on the first
 // block; HUF_repeat_check once a table was built -- level 1 never reaches HUF_repeat_valid);

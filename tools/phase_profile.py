@@ -51,6 +51,20 @@ for i, l in enumerate(ECNT):
     if buf[32 + i]:
         print(f"   {l:24s} {buf[32 + i] / R:12.2f}")
 
+# the search phase by kind of block (csrc/pgn_zenc.h zstd1_compress_wave, PhaseProf::ext)
+ext = buf[80:96]
+if ext[:12].any():
+    etot = float(buf[:16].sum())
+    print("encode search phase by kind of block, per chunk (share of the encode's wave-cycles):")
+    for name, k in (("small single-block frames (<= 2048 B)", 0), ("every other block", 6)):
+        blocks, crounds, ccyc, xrounds, xblocks, cyc = (float(v) for v in ext[k:k + 6])
+        xcyc = cyc - ccyc
+        print(f"   {name}: blocks {blocks/R:.2f}, of them into the exact search {xblocks/R:.3f}")
+        print(f"      certificate  rounds {crounds/R:8.2f}  {ccyc/R/1e3:8.1f} kcyc/chunk {100*ccyc/etot:6.2f}%")
+        print(f"      exact search rounds {xrounds/R:8.2f}  {xcyc/R/1e3:8.1f} kcyc/chunk {100*xcyc/etot:6.2f}%"
+              f"  ({xcyc/max(xrounds,1):.0f} cycles per round, entry and exit included)")
+    print(f"   small blocks searched on chip {ext[12]/R:.3f} per chunk, log overflows (searched again) {ext[13]/R:.4f}")
+
 HUF = ["tables (job flags, compact tables to LDS)", "setup + 8-iteration prologue", "trips of 8 iterations",
        "drain, head/tail bytes, last symbols, end check"]
 hp, hc = buf[64:80], buf[96:112]
