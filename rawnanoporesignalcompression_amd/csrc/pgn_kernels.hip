@@ -733,16 +733,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void de
 //   conflict-free), so block b is ring group b & 3.  An iteration consumes at most 176 bits (six
 //   dwords), so loading blocks bc + 2 and bc + 3 (bc: the block of the next dword) one iteration
 //   ahead always covers the next iteration and overwrites only consumed groups.
-// * Output: whole 128-byte lines.  A lane's 16-byte output blocks (each joins the previous and the
-//   current iteration's words with v_alignbyte, for any destination alignment) written one per
-//   iteration left 64 partial lines per wave open in L2; evicted half-written, they cost more than
-//   the decode (2.84 -> 1.63 ms per 20,000 chunks with the stores sent to one line).  So every lane
-//   starts 7 - m0 iterations late, m0 being its blocks before its first 128-byte boundary, and after
-//   an 8-iteration prologue (those blocks stored one by one) all lanes' lines end on the same
-//   iterations: the main loop runs trips of 8 iterations and stores each lane's line as 8
-//   consecutive 16-byte stores at the trip's end.
+// * Output: whole 128-byte lines.  A lane first decodes the symbols before its destination's first
+//   16-byte boundary (the head, at most 15), so each iteration's four words are an aligned block.
+//   Blocks written one per iteration left 64 partial lines per wave open in L2; evicted
+//   half-written, they cost more than the decode (2.84 -> 1.63 ms per 20,000 chunks with the stores
+//   sent to one line).  So every lane starts 7 - m0 iterations late, m0 being its blocks before its
+//   first 128-byte boundary, and after a 7-iteration prologue (those blocks stored one by one) all
+//   lanes' lines end on the same iterations: the main loop runs trips of 8 iterations and stores
+//   each lane's line as 8 consecutive 16-byte stores at the trip's end.
 // * Lanes outside their stream's iterations are frozen: their peek reads a 16-entry zero table (code
-//   length 0), their stores go to a junk line, their loads stay inside their stream.
+//   length 0), their stores go to a junk line, their loads stay inside their stream.  The trips in
+//   which no lane changes state run a body without the selects that freezing needs.
 // The head and tail bytes are byte stores.  After its symbols a stream must end exactly at its first
 // bit (the strict rule of huf_decode4_wave), else the frame's result is kDecErrHufStream.
 // ---------------------------------------------------------------------------------------------
@@ -954,24 +955,20 @@ __global__ __launch_bounds__(64) void dec_huf_kernel(DecArgs a)
         tc2 = fz ? tbZero : C2 + tbLive;
         s1 = fz ? 28u : sh1;
     };
-    // ---- output geometry: block D_m = output bytes [h + 16 m, h + 16 m + 16) at A0 + 16 m (16-byte
-    // aligned), made in the iteration after super-group m from its words (P) and the next one's (W)
-    // at byte offset h (a funnel: dword offset h / 4 by selects, byte offset h % 4 by v_alignbyte).
-    // m0 blocks precede the lane's first 128-byte boundary; the lane's super-group li runs in global
-    // iteration li + 7 - m0, so D_{m0 + 8 t + k} comes out of global iteration 8 + 8 t + k.
+    // ---- output geometry.  The lane's first h symbols (the head: the bytes before its first 16-byte
+    // boundary A0) are decoded before the iterations and stored as bytes, so super-group m (symbols
+    // h + 16 m .. h + 16 m + 15) is exactly the aligned block A0 + 16 m and an iteration's four words
+    // are stored as they are.  m0 blocks precede the lane's first 128-byte boundary; the lane's
+    // super-group li runs in global iteration li + 7 - m0, so block m0 + 8 t + k comes out of global
+    // iteration 7 + 8 t + k.
     const uint32_t h = (16u - ((uint32_t)(uintptr_t)sdst & 15u)) & 15u;  // head bytes before the first block
+    const uint32_t hh = h < nsym ? h : nsym;  // (a stream shorter than its head: no iterations)
     uint8_t* A0 = sdst + h;
-    const uint32_t rb = h & 3u;
-    const bool q1 = (h >> 2) & 1u, q2 = (h >> 3) & 1u;
     const uint32_t m0 = ((128u - ((uint32_t)(uintptr_t)A0 & 127u)) & 127u) >> 4;
     const int sft = 7 - (int)m0;
-    const int sg = (int)(nsym / 16);  // super-groups of 16 symbols
-    const int nD = sg - 1;            // whole blocks D_0 .. D_{sg-2}
-    uint32_t P[4] = {0, 0, 0, 0}, F[4] = {0, 0, 0, 0};
+    const int sg = (int)((nsym - hh) / 16);  // super-groups of 16 symbols after the head: whole blocks
     auto active = [&](int gi) { const int li = gi - sft; return li >= 0 && li < sg; };
-    // one global iteration: stage the blocks loaded an iteration ago, load the next two, decode 16
-    // symbols; returns block D_{li - 1}
-    auto iteration = [&](int gi) -> uint4 {
+    auto advance = [&]() {  // stage the blocks loaded an iteration ago, load the next two
         stage(lb[0], La[0]);
         stage(lb[0] + 1, Lb[0]);
 #pragma unroll
@@ -981,64 +978,93 @@ __global__ __launch_bounds__(64) void dec_huf_kernel(DecArgs a)
             Lb[k] = Lb[k + 1];
         }
         issue(kPf - 1);
+    };
+    // the head: an iteration of its own for the ring (at most 15 symbols, 165 bits), in pairs like
+    // every other symbol (a pair starts with at least 33 bits); a symbol the lane does not have is
+    // frozen (code length 0, nothing consumed)
+    {
+        advance();
+        const uint32_t hmax = wave_max(hh);
+        for (uint32_t j = 0; j < hmax; j += 2) {
+            freeze(j >= hh);
+            const uint32_t e0 = symbol(true);
+            freeze(j + 1 >= hh);
+            const uint32_t e1 = symbol(false);
+            refill();
+            if (j < hh) gst<uint8_t>(sdst + j, (uint8_t)(e0 >> 8));
+            if (j + 1 < hh) gst<uint8_t>(sdst + j + 1, (uint8_t)(e1 >> 8));
+        }
+        gst<uint4>(junk, make_uint4(0, 0, 0, 0));  // (the loop's pattern again: two loads, then one store)
+    }
+    // one global iteration: 16 symbols, the lane's block li = gi - sft when it is active (zeros when
+    // not).  all: every lane is either active for the whole trip or never (no selects on active)
+    auto iteration = [&](int gi, bool all) -> uint4 {
+        advance();
         uint32_t W[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) W[k] = word4();
-        // X_m = word h / 4 + m of {P, W}: two levels of per-lane selects (no indexed array, which
-        // the compiler would place in scratch)
-        const uint32_t X0 = pick4(q1, q2, P[0], P[1], P[2], P[3]), X1 = pick4(q1, q2, P[1], P[2], P[3], W[0]),
-                       X2 = pick4(q1, q2, P[2], P[3], W[0], W[1]), X3 = pick4(q1, q2, P[3], W[0], W[1], W[2]),
-                       X4 = pick4(q1, q2, W[0], W[1], W[2], W[3]);
-        const uint4 D = make_uint4(__builtin_amdgcn_alignbyte(X1, X0, rb), __builtin_amdgcn_alignbyte(X2, X1, rb),
-                                   __builtin_amdgcn_alignbyte(X3, X2, rb), __builtin_amdgcn_alignbyte(X4, X3, rb));
-        const bool act = active(gi);
-        if (gi < 8) {  // the first super-group (li = 0) falls in the prologue: its head bytes
-            const bool first = gi == sft;
-#pragma unroll
-            for (int k = 0; k < 4; k++) F[k] = cnd(first, W[k], F[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) P[k] = cnd(act, W[k], P[k]);
-        freeze(!active(gi + 1));
-        return D;
+        if (!all) freeze(!active(gi + 1));
+        return make_uint4(W[0], W[1], W[2], W[3]);
     };
     freeze(!active(0));
-    // prologue: global iterations 0 .. 7, the blocks before each lane's first line one by one
+    // prologue: global iterations 0 .. 6, the blocks before each lane's first line one by one
     // (unrolled: the in-flight slots rotate by renaming, not by copies that would wait for the loads)
 #pragma unroll
-    for (int gi = 0; gi < 8; gi++) {
-        const uint4 D = iteration(gi);
-        const int m = gi - sft - 1;
+    for (int gi = 0; gi < 7; gi++) {
+        const uint4 D = iteration(gi, false);
+        const int m = gi - sft;
 #if PGN_K2_DIAG == 1  // diagnostic (wrong output): every store to the junk line
         uint8_t* ad = junk;
 #else
-        uint8_t* ad = (m >= 0 && m < nD) ? A0 + 16 * m : junk;
+        uint8_t* ad = (m >= 0 && m < sg) ? A0 + 16 * m : junk;
 #endif
         gst<uint4>(ad, D);
     }
     // the trip loop's pattern: loads, then eight stores (so its first wait is on the loads only)
 #pragma unroll
     for (int k = 1; k < 8; k++) gst<uint4>(junk + 16 * k, make_uint4(0, 0, 0, 0));
-    // trips of 8 iterations: one whole line per lane
-    const int lines = nD > (int)m0 ? (nD - (int)m0 + 7) / 8 : 0;
+    // trips of 8 iterations: one whole line per lane.  A lane without iterations (sg == 0: no job, a
+    // bad or a short stream) keeps the zero table and its junk line throughout; the first tripsAll
+    // trips have every other lane active in all eight iterations
+    const int lines = sg > (int)m0 ? (sg - (int)m0 + 7) / 8 : 0;
     const int trips = (int)wave_max((uint32_t)lines);
-    Pp.mark(1);  // stream setup, first loads, the 8-iteration prologue
+    const int tripsAll = trips - (int)wave_max((uint32_t)(sg > 0 ? trips - (sg - (int)m0) / 8 : 0));
+    uint8_t* line = sg > 0 ? A0 + 16 * m0 : junk;  // the trip's line
+    const uint32_t lineStep = sg > 0 ? 128u : 0u;
+    Pp.mark(1);  // stream setup, first loads, the head, the 7-iteration prologue
     Pp.count(1, (uint64_t)trips);
     Pp.count(3, (uint64_t)wave_sum(nsym));
-    for (int t = 0; t < trips; t++) {
+    for (int t = 0; t < tripsAll; t++) {
         uint4 Dk[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) Dk[k] = iteration(8 + 8 * t + k);
+        for (int k = 0; k < 8; k++) Dk[k] = iteration(0, true);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+#if PGN_K2_DIAG == 1
+            uint8_t* ad = junk + 16 * k;
+#else
+            uint8_t* ad = line + 16 * k;
+#endif
+            gst<uint4>(ad, Dk[k]);
+        }
+        line += lineStep;
+    }
+    freeze(!active(7 + 8 * tripsAll));
+    for (int t = tripsAll; t < trips; t++) {
+        uint4 Dk[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) Dk[k] = iteration(7 + 8 * t + k, false);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const int m = (int)m0 + 8 * t + k;
 #if PGN_K2_DIAG == 1
             uint8_t* ad = junk + 16 * k;
 #else
-            uint8_t* ad = m < nD ? A0 + 16 * m : junk + 16 * k;
+            uint8_t* ad = m < sg ? line + 16 * k : junk + 16 * k;
 #endif
             gst<uint4>(ad, Dk[k]);
         }
+        line += lineStep;
     }
     Pp.mark(2);  // the trips of 8 iterations
 #pragma unroll
@@ -1049,15 +1075,8 @@ __global__ __launch_bounds__(64) void dec_huf_kernel(DecArgs a)
     freeze(false);
     C |= Cadd;
     Cadd = 0;
-    // the head bytes (in the first super-group) and the pending bytes of the last one
-    if (sg > 0) {
-        for (uint32_t b = 0; b < h; b++) gst<uint8_t>(sdst + b, (uint8_t)(sel4(make_uint4(F[0], F[1], F[2], F[3]), b >> 2) >> (8 * (b & 3))));
-        const uint32_t J16 = 16 * (uint32_t)sg - 16;  // first symbol of the last super-group
-        for (uint32_t b = h; b < 16; b++)
-            gst<uint8_t>(sdst + J16 + b, (uint8_t)(sel4(make_uint4(P[0], P[1], P[2], P[3]), b >> 2) >> (8 * (b & 3))));
-    }
     // the remaining symbols one by one (fewer than 16: the ring holds them)
-    for (uint32_t i = 16 * (uint32_t)sg; i < nsym; i++) {
+    for (uint32_t i = hh + 16 * (uint32_t)sg; i < nsym; i++) {
         const uint32_t ent = symbol(true);
         refill();
         gst<uint8_t>(sdst + i, (uint8_t)(ent >> 8));
