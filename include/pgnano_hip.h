@@ -777,6 +777,100 @@ int pgn_base_qual_device(pgn_ctx *ctx, const pgn_qual_params *params, size_t nre
                          const uint64_t *d_read_bases, const uint32_t *d_base_frame, const int32_t *d_read_status,
                          uint8_t *d_qual, uint64_t base_capacity, void *stream);
 
+/* ---- FASTQ records ------------------------------------------------------------------------------------------
+ * The last two steps of the route above:
+ *   ... -> pgn_collapse_codes_device -> pgn_base_qual_device -> pgn_read_qual_device -> pgn_fastq_records_device
+ * A read's mean quality with a pass flag, and the kept reads as FASTQ text in one device buffer with per-read
+ * offsets, so that the result goes to a file with one download and one write().  Both rules are integer and byte
+ * rules: the tolerance is zero.  No outside source defines the rule, so this text does.
+ *
+ * pgn_read_qual_device.  d_read_bases (nreads + 1, non-decreasing) and d_read_status are what
+ * pgn_collapse_codes_device left, d_qual what pgn_base_qual_device wrote, base_capacity the size of d_qual.
+ * A read "has input" iff its status is PGN_OK, read_bases[r] <= read_bases[r+1] <= base_capacity and
+ *   m = read_bases[r+1] - read_bases[r] > 0.
+ * For a read with input:
+ *   s = skip_bases if m > skip_bases else 0, and n = m - s
+ * (the leading bases of a read are the adapter's neighbours, and basecallers leave them out of the mean);
+ *   U = sum over g in [s, m) of err[min(max(qual[read_bases[r] + g], 33), 126) - 33]      (uint64; n < 2^32, so
+ *       it cannot wrap)
+ *   mean_q[r] = q_min + #{ j < nthresholds : U <= (uint64)thr[j] * n }
+ *   pass[r] = mean_q[r] >= min_mean_q                                                      (1 or 0)
+ * and err_sum[r] = U.  For every other read mean_q = 0, err_sum = 0 and pass = 0.  All three arrays are written for
+ * every read, so they are defined after the call; d_err_sum may be NULL.  d_mean_q is uint32 so that it can be a tag
+ * column of the record call.  Parameters (pgn_read_qual_params): `mean` holds q_min, nthresholds and thr with the
+ * conditions of pgn_base_qual_device; err[q] is the error of phred character 33 + q in units of 2^-32: the
+ * package's err_table builds err[q] = min(2^32 - 1, rint(2^32 * 10^(-q/10))), and qual_thresholds builds thr.  The
+ * comparison is the one pgn_base_qual_device uses; the mean is of error probabilities, not of qualities.
+ * The work is flat over the bases in tiles of PGN_READ_QUAL_TILE_BASES, tile k being bases [k * tile, (k+1) * tile)
+ * of d_qual; the sum is of integers, so its split over tiles changes nothing.  If d_read_bases decreases anywhere
+ * the three outputs are unspecified, but no access leaves the buffers and the call ends.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx or params; the `mean` conditions;
+ * nreads >= 2^32; with nreads > 0 a NULL d_read_bases, d_read_status, d_mean_q or d_pass; with base_capacity > 0 a
+ * NULL d_qual.  nreads == 0 returns PGN_OK and touches nothing.  Asynchronous on `stream`, no host wait; the
+ * scratch, when d_err_sum is NULL, is 8 bytes per read on the context.
+ *
+ * pgn_fastq_records_device.  A read is kept iff its status is PGN_OK, read_bases[r] <= read_bases[r+1] <=
+ * base_capacity, m > 0, and d_keep is NULL or d_keep[r] != 0.  d_keep is `pass` of the call above or anything of
+ * the caller's: the complement of a mask writes the fail file with a second call.
+ * Record of a kept read, byte for byte:
+ *   '@' uuid { '\t' name0 name1 ':' 'i' ':' dec(tag_k[r]) } '\n' SEQ '\n' '+' '\n' QUAL '\n'
+ * uuid: the 36 characters of d_read_ids[16 r ..], the 16 bytes in order as lowercase hex with '-' after bytes 4, 6,
+ * 8 and 10 (Python's str(uuid.UUID(bytes=...))).  Tags: ntags <= PGN_FASTQ_MAX_TAGS columns k = 0 .. ntags - 1 in
+ * order, each a two-byte name ([A-Za-z][A-Za-z0-9]) and a device array of nreads uint32, the value written in
+ * decimal without leading zeros.  SEQ / QUAL: the read's m bytes of d_seq / d_qual; with PGN_FASTQ_REVERSE in flags
+ * both are written in reverse order (direct RNA reads are sequenced 3' to 5'; the alphabet is
+ * pgn_collapse_codes_device's business).
+ *   length of a kept read's record = 42 + 2m + sum_k (6 + digits(tag_k[r])); a read that is not kept has length 0.
+ * d_rec_off (nreads + 1, uint64) is the exclusive scan of the lengths.  It always holds the full counts, so
+ * rec_off[nreads] is the capacity that would have sufficed.  A kept read with rec_off[r+1] > byte_capacity gets
+ * rec_status PGN_ERR_DST_TOO_SMALL and no byte of it is written: there are no partial records.  A kept read that
+ * is written gets PGN_OK, its record at d_out + rec_off[r].  A read that is not kept gets its own status if that is
+ * non-zero, else PGN_OK.  Nothing outside the written records is touched, and no byte outside the kept reads'
+ * [read_bases[r], read_bases[r+1]) ranges of d_seq and d_qual, their ids and their tag entries is read.
+ *   fastq_bound(nreads, nbases, ntags) = nreads * (42 + 16 * ntags) + 2 * nbases
+ * gives the host a capacity without a wait.  d_out may have any alignment.  The writer is flat over the output
+ * bytes: a workgroup owns the PGN_FASTQ_TILE_BYTES bytes between two addresses that are multiples of that constant
+ * apart, counted from d_out rounded down to 16, so with d_out a multiple of 16 the seams lie at the output offsets
+ * k * PGN_FASTQ_TILE_BYTES.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx or params; unknown flag bits; ntags >
+ * PGN_FASTQ_MAX_TAGS or a bad name among the first ntags; nreads >= 2^32; with nreads > 0 a NULL d_read_ids,
+ * d_read_bases, d_read_status, d_rec_status, or a NULL d_tag[k] for k < ntags; a NULL d_rec_off; with
+ * base_capacity > 0 a NULL d_seq or d_qual; with byte_capacity > 0 a NULL d_out.  nreads == 0 writes
+ * rec_off[0] = 0 only.  Asynchronous on `stream`, no host wait; the scratch is 8 bytes per 1,024 reads.
+ *
+ * Not covered: SAM/uBAM output, and the move-table tag; a float qs:f: tag; compression of the text; pass and fail
+ * files from one call; records for the CTC path's bases without qualities; signed or 64-bit tag values; splitting
+ * of reads. */
+#define PGN_READ_QUAL_TILE_BASES 4096u
+#define PGN_FASTQ_TILE_BYTES 16384u
+#define PGN_FASTQ_MAX_TAGS 8u
+#define PGN_FASTQ_REVERSE 1u
+
+typedef struct pgn_read_qual_params {
+    pgn_qual_params mean;   /* q_min, nthresholds, thr: as for pgn_base_qual_device */
+    uint32_t skip_bases;    /* leading bases left out of the mean of a read longer than this */
+    uint32_t min_mean_q;    /* pass = mean_q >= min_mean_q */
+    uint32_t err[94];       /* the error of phred character 33 + q in units of 2^-32 */
+} pgn_read_qual_params;
+
+typedef struct pgn_fastq_params {
+    uint32_t flags;                 /* PGN_FASTQ_REVERSE or 0 */
+    uint32_t ntags;                 /* <= PGN_FASTQ_MAX_TAGS */
+    uint8_t  tag_name[8][2];        /* [A-Za-z][A-Za-z0-9] for the first ntags; the rest is not read */
+    const uint32_t *d_tag[8];       /* nreads values each for the first ntags; the rest is not read */
+} pgn_fastq_params;
+
+int pgn_read_qual_device(pgn_ctx *ctx, const pgn_read_qual_params *params, size_t nreads,
+                         const uint64_t *d_read_bases, const int32_t *d_read_status, const uint8_t *d_qual,
+                         uint64_t base_capacity, uint32_t *d_mean_q, uint64_t *d_err_sum /* may be NULL */,
+                         uint8_t *d_pass, void *stream);
+
+int pgn_fastq_records_device(pgn_ctx *ctx, const pgn_fastq_params *params, size_t nreads, const uint8_t *d_read_ids,
+                             const uint64_t *d_read_bases, const int32_t *d_read_status,
+                             const uint8_t *d_keep /* may be NULL */, const uint8_t *d_seq, const uint8_t *d_qual,
+                             uint64_t base_capacity, uint8_t *d_out, uint64_t byte_capacity, uint64_t *d_rec_off,
+                             int32_t *d_rec_status, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

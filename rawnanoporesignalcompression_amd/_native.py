@@ -120,6 +120,24 @@ class QualParams(C.Structure):
     _fields_ = [("q_min", C.c_uint32), ("nthresholds", C.c_uint32), ("thr", C.c_uint32 * PGN_QUAL_MAX)]
 
 
+PGN_READ_QUAL_TILE_BASES = 4096
+PGN_FASTQ_TILE_BYTES = 16384
+PGN_FASTQ_MAX_TAGS = 8
+PGN_FASTQ_REVERSE = 1
+
+
+class ReadQualParams(C.Structure):
+    """pgn_read_qual_params"""
+    _fields_ = [("mean", QualParams), ("skip_bases", C.c_uint32), ("min_mean_q", C.c_uint32),
+                ("err", C.c_uint32 * (PGN_QUAL_MAX + 1))]
+
+
+class FastqParams(C.Structure):
+    """pgn_fastq_params"""
+    _fields_ = [("flags", C.c_uint32), ("ntags", C.c_uint32), ("tag_name", (C.c_uint8 * 2) * PGN_FASTQ_MAX_TAGS),
+                ("d_tag", C.c_void_p * PGN_FASTQ_MAX_TAGS)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -199,6 +217,11 @@ SIGNATURES = [
      [_VP, C.POINTER(CrfParams), C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.c_uint64, _VP, C.c_uint64, _VP]),
     ("pgn_base_qual_device", C.c_int,
      [_VP, C.POINTER(QualParams), _SZ, _U64P, _VP, _VP, C.c_uint64, C.c_uint64, _U64P, _U32P, _I32P, _VP, C.c_uint64,
+      _VP]),
+    ("pgn_read_qual_device", C.c_int,
+     [_VP, C.POINTER(ReadQualParams), _SZ, _U64P, _I32P, _VP, C.c_uint64, _U32P, _U64P, _VP, _VP]),
+    ("pgn_fastq_records_device", C.c_int,
+     [_VP, C.POINTER(FastqParams), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, _I32P,
       _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,

@@ -24,6 +24,7 @@
 #include "pgn_crf.h"
 #include "pgn_crf_post.h"
 #include "pgn_qual.h"
+#include "pgn_fastq.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2158,6 +2159,9 @@ struct pgn_ctx {
     // vectors (crf::post_row_scratch_bytes per row) in the same memory under the same cap: a call sequence of the
     // context follows the one before it, so the two never hold it at once.
     DevBuf<uint32_t> crfBp{bufs};
+    // pgn_read_qual_device: the reads' error sums when the caller passes no array.  pgn_fastq_records_device: the
+    // totals of the length kernel's workgroups, their sum and the end of the written records
+    DevBuf<uint64_t> fqWork{bufs};
     uint64_t crfCap = crf::kDefaultScratch;
     int crfTrace = 0;  // 0 in the row's workgroup, 1 split, 2 none
     // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
@@ -3950,6 +3954,110 @@ extern "C" int pgn_base_qual_device(pgn_ctx* c, const pgn_qual_params* params, s
     hipLaunchKernelGGL(qual::base_qual_kernel, dim3((unsigned)std::min<uint64_t>(nreads, 1u << 20)), dim3(qual::kThreads), 0,
                        sc.s, a);
     HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+// ---- mean quality and FASTQ records (pgn_fastq.h) ----------------------------------------------------------
+extern "C" int pgn_read_qual_device(pgn_ctx* c, const pgn_read_qual_params* params, size_t nreads,
+                                    const uint64_t* d_read_bases, const int32_t* d_read_status, const uint8_t* d_qual,
+                                    uint64_t base_capacity, uint32_t* d_mean_q, uint64_t* d_err_sum, uint8_t* d_pass,
+                                    void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!qual::params_valid(&params->mean)) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    if (nreads && (!d_read_bases || !d_read_status || !d_mean_q || !d_pass)) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && !d_qual) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    if (!d_err_sum) {
+        const int rc = reserve(c, {{c->fqWork, nreads * sizeof(uint64_t)}});
+        if (rc != PGN_OK) return rc;
+    }
+    fastq::QualArgs a{};
+    a.nreads = nreads;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.qual = d_qual;
+    a.baseCapacity = base_capacity;
+    a.acc = d_err_sum ? d_err_sum : static_cast<uint64_t*>(c->fqWork);
+    a.meanQ = d_mean_q;
+    a.errSum = d_err_sum;
+    a.pass = d_pass;
+    a.prm = *params;
+    HIPCHK(hipMemsetAsync(a.acc, 0, nreads * sizeof(uint64_t), s));
+    const uint64_t ntiles = (base_capacity + fastq::kQualTile - 1) / fastq::kQualTile;
+    for (a.tileBase = 0; a.tileBase < ntiles; a.tileBase += 1u << 30) {  // a grid holds fewer than 2^31 tiles
+        const uint64_t n = std::min<uint64_t>(ntiles - a.tileBase, 1u << 30);
+        hipLaunchKernelGGL(fastq::read_qual_sum_kernel, dim3((unsigned)n), dim3(fastq::kThreads), 0, s, a);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(fastq::read_qual_finish_kernel, dim3((unsigned)(nreads / 256 + 1)), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+extern "C" int pgn_fastq_records_device(pgn_ctx* c, const pgn_fastq_params* params, size_t nreads,
+                                        const uint8_t* d_read_ids, const uint64_t* d_read_bases,
+                                        const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq,
+                                        const uint8_t* d_qual, uint64_t base_capacity, uint8_t* d_out,
+                                        uint64_t byte_capacity, uint64_t* d_rec_off, int32_t* d_rec_status, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!fastq::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    if (nreads) {
+        if (!d_read_ids || !d_read_bases || !d_read_status || !d_rec_status) return PGN_ERR_INVALID_ARG;
+        for (uint32_t k = 0; k < params->ntags; k++)
+            if (!params->d_tag[k]) return PGN_ERR_INVALID_ARG;
+    }
+    if (!d_rec_off) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && (!d_seq || !d_qual)) return PGN_ERR_INVALID_ARG;
+    if (byte_capacity && !d_out) return PGN_ERR_INVALID_ARG;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    if (nreads == 0) {
+        HIPCHK(hipMemsetAsync(d_rec_off, 0, sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    fastq::RecArgs a{};
+    a.nreads = nreads;
+    a.ids = d_read_ids;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.keep = d_keep;
+    a.seq = d_seq;
+    a.qual = d_qual;
+    a.baseCapacity = base_capacity;
+    a.out = d_out;
+    a.byteCapacity = byte_capacity;
+    a.recOff = d_rec_off;
+    a.recStatus = d_rec_status;
+    a.nblocks = (nreads + fastq::kScanThreads - 1) / fastq::kScanThreads;
+    a.mis = (uint32_t)((uintptr_t)d_out & 15u);
+    a.ntiles = byte_capacity ? (byte_capacity + a.mis + fastq::kTile - 1) / fastq::kTile : 0;
+    a.prm = *params;
+    const int rc = reserve(c, {{c->fqWork, (size_t)(a.nblocks + 2) * sizeof(uint64_t)}});
+    if (rc != PGN_OK) return rc;
+    a.blockSums = c->fqWork;
+    hipLaunchKernelGGL(fastq::fastq_len_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    stitch::PlanArgs top{};  // the scan of the workgroups' totals is the stitch plan's
+    top.blockSums = a.blockSums;
+    top.nblocks = a.nblocks;
+    hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, top);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(fastq::fastq_offset_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (a.ntiles) {
+        // tiles behind the written records end at once, so a capacity far above the text costs little
+        const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, 1u << 24);
+        hipLaunchKernelGGL(fastq::fastq_write_kernel, dim3(grid), dim3(fastq::kThreads), 0, s, a);
+        HIPCHK(hipGetLastError());
+    }
     return PGN_OK;
 }
 

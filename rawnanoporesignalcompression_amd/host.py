@@ -445,3 +445,124 @@ def base_qual_signal(codes, post, base_frame, n_frames, thresholds, q_min):
             U, n = sum(int(v) for v in u), t1 - t0
             out[g] = 33 + prm.q_min + sum(1 for v in thr if U <= v * n)
     return out
+
+
+# ---- FASTQ records: mean quality, filter and layout ------------------------------------------------------------
+def err_table():
+    """``err[q] = min(2^32 - 1, rint(2^32 * 10^(-q/10)))`` for ``q`` in ``0..93``, uint32: the error of phred
+    character ``33 + q`` in units of 2^-32, the table :func:`read_qual_signal` sums."""
+    q = np.arange(_native.PGN_QUAL_MAX + 1, dtype=np.float64)
+    return np.minimum(np.rint(2.0 ** 32 * 10.0 ** (-q / 10.0)), 2.0 ** 32 - 1).astype(np.uint32)
+
+
+def read_qual_params(thresholds=None, q_min=1, skip_bases=60, min_mean_q=0, err=None):
+    """``pgn_read_qual_params``: :func:`qual_params` of ``thresholds`` and ``q_min``, the leading bases left out of
+    a longer read's mean, the quality a read needs to pass, and ``err`` (default :func:`err_table`)."""
+    err = err_table() if err is None else np.asarray(err)
+    if err.shape != (_native.PGN_QUAL_MAX + 1,) or err.min() < 0 or err.max() > 0xFFFFFFFF:
+        raise ValueError(f"err must hold {_native.PGN_QUAL_MAX + 1} uint32 values")
+    skip_bases, min_mean_q = int(skip_bases), int(min_mean_q)
+    if not (0 <= skip_bases <= 0xFFFFFFFF and 0 <= min_mean_q <= 0xFFFFFFFF):
+        raise ValueError("skip_bases and min_mean_q must be uint32 values")
+    p = _native.ReadQualParams(qual_params(thresholds, q_min), skip_bases, min_mean_q)
+    p.err[:] = [int(v) for v in err]
+    return p
+
+
+def _read_ranges(read_bases, status, base_capacity):
+    """Per read ``(b0, m)`` with ``m > 0`` where the read has bases inside the capacity and no status, else
+    ``(b0, 0)``."""
+    rb = [int(v) for v in np.asarray(read_bases).reshape(-1)]
+    st = [int(v) for v in np.asarray(status).reshape(-1)]
+    if len(rb) != len(st) + 1:
+        raise ValueError("read_bases must hold one entry more than status")
+    return [(rb[r], rb[r + 1] - rb[r] if st[r] == 0 and rb[r] < rb[r + 1] <= base_capacity else 0) for r in range(len(st))]
+
+
+def read_qual_signal(qual, read_bases, status, thresholds, *, q_min, skip_bases, min_mean_q, err=None,
+                     base_capacity=None):
+    """Mean quality and pass flag of every read on the host (include/pgnano_hip.h, the rule of
+    pgn_read_qual_device): ``qual`` the phred characters of all reads, read ``r``'s at ``qual[read_bases[r]:
+    read_bases[r + 1]]``.  A read with status 0 and ``m > 0`` bases inside ``base_capacity`` (default
+    ``len(qual)``) leaves out its first ``skip_bases`` bases if it has more than that, sums ``err`` (default
+    :func:`err_table`) of the others' characters, clamped to ``'!'..'~'``, into ``U``, and gets ``q_min + #{j : U <=
+    thresholds[j] * n}`` over its ``n`` counted bases.  Returns ``(mean_q uint32, err_sum uint64, passed uint8)``,
+    all zero for every other read."""
+    qual = np.asarray(qual, dtype=np.uint8).reshape(-1)
+    cap = len(qual) if base_capacity is None else int(base_capacity)
+    prm = read_qual_params(thresholds, q_min, skip_bases, min_mean_q, err)
+    thr = [int(v) for v in prm.mean.thr[:prm.mean.nthresholds]]
+    table = [int(v) for v in prm.err]
+    ranges = _read_ranges(read_bases, status, cap)
+    mean_q, err_sum = np.zeros(len(ranges), np.uint32), np.zeros(len(ranges), np.uint64)
+    passed = np.zeros(len(ranges), np.uint8)
+    for r, (b0, m) in enumerate(ranges):
+        if m == 0:
+            continue
+        s = prm.skip_bases if m > prm.skip_bases else 0
+        U = sum(table[min(max(int(c), 33), 126) - 33] for c in qual[b0 + s:b0 + m])
+        q = prm.mean.q_min + sum(1 for v in thr if U <= v * (m - s))
+        mean_q[r], err_sum[r], passed[r] = q, U, q >= prm.min_mean_q
+    return mean_q, err_sum, passed
+
+
+def fastq_bound(nreads, nbases, ntags=0) -> int:
+    """Bytes that hold the records of ``nreads`` reads with ``nbases`` bases in all and ``ntags`` tags each:
+    ``nreads * (42 + 16 * ntags) + 2 * nbases`` (a tag is at most 6 bytes and 10 digits)."""
+    return int(nreads) * (42 + 16 * int(ntags)) + 2 * int(nbases)
+
+
+def _fastq_tags(tags, nreads):
+    """``[(name bytes, uint32 values)]`` of a record call's tags, checked."""
+    items = list(tags.items()) if hasattr(tags, "items") else list(tags or ())
+    if len(items) > _native.PGN_FASTQ_MAX_TAGS:
+        raise ValueError(f"at most {_native.PGN_FASTQ_MAX_TAGS} tags")
+    out = []
+    for name, values in items:
+        name = name.encode("ascii") if isinstance(name, str) else bytes(name)
+        if len(name) != 2 or not (chr(name[0]).isalpha() and chr(name[1]).isalnum()) or max(name) > 127:
+            raise ValueError(f"a tag's name is [A-Za-z][A-Za-z0-9] (got {name!r})")
+        v = np.asarray(values).reshape(-1)
+        if len(v) != nreads or (len(v) and (int(v.min()) < 0 or int(v.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"tag {name.decode()} must hold {nreads} uint32 values")
+        out.append((name, v))
+    return out
+
+
+def fastq_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=None, reverse=False, base_capacity=None,
+                         byte_capacity=None):
+    """The FASTQ text of a batch on the host (include/pgnano_hip.h, the rule of pgn_fastq_records_device).  A
+    read is kept if its status is 0, it has ``m > 0`` bases inside ``base_capacity`` (default ``len(seq)``) and
+    ``keep`` is None or ``keep[r]`` is not 0; its record is ``@uuid``, a ``\\tXX:i:value`` per tag (``tags``: a dict
+    or pairs of two-character name and per-read uint32 values), a newline, its ``m`` bytes of ``seq``, ``\\n+\\n``,
+    its bytes of ``qual`` and a newline, both strings backwards with ``reverse``.  Returns ``(text, rec_off,
+    rec_status)``: ``rec_off`` (uint64, reads + 1) is the scan of all lengths whatever ``byte_capacity`` is; a
+    record that ends above ``byte_capacity`` (default: none does) is left out with status 1
+    (PGN_ERR_DST_TOO_SMALL), a read that is not kept has its own status, and ``text`` is the written records."""
+    ids = np.asarray(read_ids, dtype=np.uint8).reshape(-1, 16)
+    seq, qual = np.asarray(seq, dtype=np.uint8).reshape(-1), np.asarray(qual, dtype=np.uint8).reshape(-1)
+    cap = len(seq) if base_capacity is None else int(base_capacity)
+    ranges = _read_ranges(read_bases, status, cap)
+    n = len(ranges)
+    if len(ids) != n:
+        raise ValueError("read_ids must hold 16 bytes per read")
+    cols = _fastq_tags(tags, n)
+    keep = None if keep is None else np.asarray(keep).reshape(-1)
+    hexd = "0123456789abcdef"
+    rec_off, rec_status = np.zeros(n + 1, np.uint64), np.asarray(status).astype(np.int32).reshape(-1).copy()
+    text, at = [], 0
+    for r, (b0, m) in enumerate(ranges):
+        if m and (keep is None or keep[r] != 0):
+            h = "".join(hexd[b >> 4] + hexd[b & 15] for b in ids[r].tolist())
+            rec = bytearray(b"@" + "-".join((h[:8], h[8:12], h[12:16], h[16:20], h[20:])).encode())
+            for name, v in cols:
+                rec += b"\t" + name + b":i:" + str(int(v[r])).encode()
+            s, q = seq[b0:b0 + m], qual[b0:b0 + m]
+            rec += b"\n" + (s[::-1] if reverse else s).tobytes() + b"\n+\n" + (q[::-1] if reverse else q).tobytes() + b"\n"
+            fits = byte_capacity is None or at + len(rec) <= int(byte_capacity)
+            rec_status[r] = _native.PGN_OK if fits else _native.PGN_ERR_DST_TOO_SMALL
+            if fits:
+                text.append(bytes(rec))
+            at += len(rec)
+        rec_off[r + 1] = at
+    return b"".join(text), rec_off, rec_status
