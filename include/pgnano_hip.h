@@ -871,6 +871,90 @@ int pgn_fastq_records_device(pgn_ctx *ctx, const pgn_fastq_params *params, size_
                              uint64_t base_capacity, uint8_t *d_out, uint64_t byte_capacity, uint64_t *d_rec_off,
                              int32_t *d_rec_status, void *stream);
 
+/* ---- BAM records --------------------------------------------------------------------------------------------
+ * The other end of the same route: the kept reads as unaligned BAM records with the move table, laid out raw or
+ * in BGZF blocks, so that the file is header + one download per batch + the end marker.
+ *   ... -> pgn_base_qual_device -> pgn_read_qual_device -> pgn_bam_records_device
+ * The rule is the SAM/BAM specification's (SAMv1 section 4.2 for the record, 4.1 for BGZF); no outside program
+ * defines the bytes here, so this text does.  Integers and bytes alone: the tolerance is zero.
+ *
+ * pgn_bam_records_device.  The inputs are those of pgn_fastq_records_device, and for the move table d_read_frames
+ * (nreads + 1), d_codes, frame_base and frame_capacity with the window meaning they have in pgn_base_qual_device:
+ * d_codes[i - frame_base] is frame i's code.  A read is kept iff its status is PGN_OK, read_bases[r] <=
+ * read_bases[r+1] <= base_capacity, m > 0, and d_keep is NULL or d_keep[r] != 0.  With PGN_BAM_MOVES a read that
+ * would be kept must also have its frames [read_frames[r], read_frames[r+1]) inside [frame_base, frame_base +
+ * frame_capacity), and F = read_frames[r+1] - read_frames[r] < 2^31 of them; a read that fails either is not kept
+ * and gets PGN_ERR_INVALID_ARG.
+ * Record of a kept read, little-endian, byte for byte:
+ *   block_size u32 = the record's length minus 4
+ *   refID i32 = -1, pos i32 = -1, l_read_name u8 = 37, mapq u8 = 0, bin u16 = 4680, n_cigar_op u16 = 0,
+ *   flag u16 = 4, l_seq u32 = m, next_refID i32 = -1, next_pos i32 = -1, tlen i32 = 0
+ *   read_name: the 36 uuid characters of the FASTQ rule, then NUL.  No CIGAR.
+ *   seq: (m + 1) / 2 bytes, base 2i in the high nibble and base 2i+1 in the low nibble, the low nibble of the
+ *     last byte of an odd read 0; a nibble is the position of the upper-cased character in "=ACMGRSVTWYHKDBN",
+ *     and 15 for any other byte.
+ *   qual: m bytes, min(max(q, 33), 126) - 33; with d_qual == NULL every byte is 0xFF.
+ *   tags: for each column k < ntags, name0 name1 'I' and the uint32 (7 bytes); with PGN_BAM_MOVES, last,
+ *     'm' 'v' 'B' 'c', u32 count 1 + F, stride as int8, then F bytes (codes[read_frames[r] - frame_base + f] >> 7) & 1.
+ * PGN_BAM_REVERSE reverses the order of bases and of qualities before packing.  The move table stays in signal
+ * order: it is not reversed.
+ *   block_size of a kept read = 69 + (m + 1) / 2 + m + 7 * ntags + (moves ? 9 + F : 0),
+ *   length of its record = block_size + 4, at least 75; a read that is not kept has length 0.
+ * The length depends on m, F and ntags alone.  d_rec_off (nreads + 1, uint64) is the exclusive scan of the lengths
+ * and always holds the full counts.  A kept read whose record ends above the stream capacity gets
+ * PGN_ERR_DST_TOO_SMALL and no byte: there are no partial records.  The offsets are non-decreasing, so the written
+ * records are a prefix of the stream; W, the largest rec_off[r+1] within the capacity, is d_written[0].  A kept read
+ * that is written gets PGN_OK; a read that is not kept its own status, or PGN_ERR_INVALID_ARG as above.
+ * Two layouts:
+ *   Raw (without PGN_BAM_BGZF): stream byte o is d_out[o], the stream capacity is byte_capacity, d_written[1] = W.
+ *   PGN_BAM_BGZF: the stream is cut every PGN_BGZF_BLOCK_BYTES = 65,280 bytes (htslib's 0xff00).  Stream byte o is
+ *     d_out[(o / 65280) * 65311 + 23 + o % 65280].  Block k < ceil(W / 65280) with payload length n gets the header
+ *       1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00, BSIZE = n + 30 as u16,
+ *     the stored-deflate prefix 01, n as u16, ~n as u16, and behind the payload CRC32(payload) (the zlib polynomial,
+ *     reflected 0xEDB88320) and n, both u32.  The stream capacity is the largest S with S + 31 * ceil(S / 65280) <=
+ *     byte_capacity; d_written[1] = W + 31 * ceil(W / 65280).  W == 0 writes no block; the last block is short.
+ *     The records of one call form a self-contained run of blocks, so batches concatenate behind a BGZF block
+ *     with the BAM header and in front of the 28-byte end marker, which the caller writes.
+ * Nothing at or beyond d_out + d_written[1] is touched, and nothing in front of d_out; d_out may have any alignment.
+ *   bam_bound(nreads, nbases, ntags, nframes) = nreads * (74 + 7 * ntags) + nbases + nbases / 2 [+ 9 * nreads + nframes]
+ *   bgzf_bound(nbytes) = nbytes + 31 * ceil(nbytes / 65280)
+ * give the host a capacity without a wait.  The writer is flat over the stream, a workgroup per 65,280 stream bytes
+ * in either layout; with PGN_BAM_BGZF it checksums the block it holds in LDS before it stores it.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx or params; unknown flag bits; ntags >
+ * PGN_BAM_MAX_TAGS or a bad name among the first ntags ([A-Za-z][A-Za-z0-9]); with PGN_BAM_MOVES a stride outside
+ * 1..127; nreads >= 2^32; with nreads > 0 a NULL d_read_ids, d_read_bases, d_read_status, d_rec_status, a NULL
+ * d_tag[k] for k < ntags, or with PGN_BAM_MOVES a NULL d_read_frames; a NULL d_rec_off or d_written; with
+ * base_capacity > 0 a NULL d_seq; with PGN_BAM_MOVES and frame_capacity > 0 a NULL d_codes; with byte_capacity > 0
+ * a NULL d_out.  d_qual may be NULL; d_codes and d_read_frames may be NULL without PGN_BAM_MOVES.  nreads == 0
+ * writes rec_off[0] = 0 and d_written = {0, 0} only.  Asynchronous on `stream`, no host wait; the scratch is 8 bytes
+ * per 1,024 reads.
+ *
+ * Not covered: deflate compression (every block holds a stored deflate block, as `samtools view -u` writes);
+ * aligned records and reference headers; qs:f and other non-uint32 tags; a reversed move table; SAM text; BGZF
+ * framing of other buffers. */
+#define PGN_BAM_MAX_TAGS 8u
+#define PGN_BAM_REVERSE 1u
+#define PGN_BAM_MOVES 2u
+#define PGN_BAM_BGZF 4u
+#define PGN_BGZF_BLOCK_BYTES 65280u
+
+typedef struct pgn_bam_params {
+    uint32_t flags;                 /* PGN_BAM_REVERSE | PGN_BAM_MOVES | PGN_BAM_BGZF */
+    uint32_t ntags;                 /* <= PGN_BAM_MAX_TAGS */
+    uint8_t  tag_name[8][2];        /* [A-Za-z][A-Za-z0-9] for the first ntags; the rest is not read */
+    const uint32_t *d_tag[8];       /* nreads values each for the first ntags; the rest is not read */
+    uint32_t stride;                /* 1..127 with PGN_BAM_MOVES: the model's stride, the move table's first entry */
+    uint32_t pad;
+} pgn_bam_params;
+
+int pgn_bam_records_device(pgn_ctx *ctx, const pgn_bam_params *params, size_t nreads, const uint8_t *d_read_ids,
+                           const uint64_t *d_read_bases, const int32_t *d_read_status,
+                           const uint8_t *d_keep /* may be NULL */, const uint8_t *d_seq,
+                           const uint8_t *d_qual /* may be NULL */, uint64_t base_capacity,
+                           const uint64_t *d_read_frames, const uint8_t *d_codes, uint64_t frame_base,
+                           uint64_t frame_capacity, uint8_t *d_out, uint64_t byte_capacity, uint64_t *d_rec_off,
+                           int32_t *d_rec_status, uint64_t *d_written, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

@@ -138,6 +138,17 @@ class FastqParams(C.Structure):
                 ("d_tag", C.c_void_p * PGN_FASTQ_MAX_TAGS)]
 
 
+PGN_BAM_MAX_TAGS = 8
+PGN_BAM_REVERSE, PGN_BAM_MOVES, PGN_BAM_BGZF = 1, 2, 4
+PGN_BGZF_BLOCK_BYTES = 65280
+
+
+class BamParams(C.Structure):
+    """pgn_bam_params"""
+    _fields_ = [("flags", C.c_uint32), ("ntags", C.c_uint32), ("tag_name", (C.c_uint8 * 2) * PGN_BAM_MAX_TAGS),
+                ("d_tag", C.c_void_p * PGN_BAM_MAX_TAGS), ("stride", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -223,6 +234,9 @@ SIGNATURES = [
     ("pgn_fastq_records_device", C.c_int,
      [_VP, C.POINTER(FastqParams), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, _I32P,
       _VP]),
+    ("pgn_bam_records_device", C.c_int,
+     [_VP, C.POINTER(BamParams), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _U64P, _VP, C.c_uint64, C.c_uint64,
+      _VP, C.c_uint64, _U64P, _I32P, _U64P, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

@@ -25,6 +25,7 @@
 #include "pgn_crf_post.h"
 #include "pgn_qual.h"
 #include "pgn_fastq.h"
+#include "pgn_bam.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2160,8 +2161,11 @@ struct pgn_ctx {
     // context follows the one before it, so the two never hold it at once.
     DevBuf<uint32_t> crfBp{bufs};
     // pgn_read_qual_device: the reads' error sums when the caller passes no array.  pgn_fastq_records_device: the
-    // totals of the length kernel's workgroups, their sum and the end of the written records
+    // totals of the length kernel's workgroups, their sum and the end of the written records; pgn_bam_records_device:
+    // the same totals and their sum.  PGN_BAM_CRC=split moves the BGZF checksum into a kernel of its own
+    // (measurements only: the bytes are the same)
     DevBuf<uint64_t> fqWork{bufs};
+    bool bamCrcSplit = false;
     uint64_t crfCap = crf::kDefaultScratch;
     int crfTrace = 0;  // 0 in the row's workgroup, 1 split, 2 none
     // the selection of long reads in parts (pgn_select.h, pgn_ctx_set_select_split): the head, the slots'
@@ -2279,6 +2283,7 @@ static int ctx_init(pgn_ctx* c)
     if (const char* v = getenv("PGN_HUF_WIDE_LAST")) { const long x = atol(v); if (x >= 0) c->hufWideLast = (size_t)x; }
     if (const char* v = getenv("PGN_HUF_PRIO_LAST")) c->hufPrioLast = v[0] == '1';
     if (const char* v = getenv("PGN_CRF_TRACEBACK")) c->crfTrace = strcmp(v, "split") == 0 ? 1 : strcmp(v, "none") == 0 ? 2 : 0;
+    if (const char* v = getenv("PGN_BAM_CRC")) c->bamCrcSplit = strcmp(v, "split") == 0;
     if (const char* v = getenv("PGN_DEFER_TAIL_PLAIN")) { const long x = atol(v); if (x >= 0) c->deferTailPlain = (size_t)x; }
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const char* pe = getenv("PGN_PHASE_PROFILE");
@@ -4057,6 +4062,83 @@ extern "C" int pgn_fastq_records_device(pgn_ctx* c, const pgn_fastq_params* para
         const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, 1u << 24);
         hipLaunchKernelGGL(fastq::fastq_write_kernel, dim3(grid), dim3(fastq::kThreads), 0, s, a);
         HIPCHK(hipGetLastError());
+    }
+    return PGN_OK;
+}
+
+// ---- BAM records (pgn_bam.h) ----------------------------------------------------------------------------------
+extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, size_t nreads, const uint8_t* d_read_ids,
+                                      const uint64_t* d_read_bases, const int32_t* d_read_status, const uint8_t* d_keep,
+                                      const uint8_t* d_seq, const uint8_t* d_qual, uint64_t base_capacity,
+                                      const uint64_t* d_read_frames, const uint8_t* d_codes, uint64_t frame_base,
+                                      uint64_t frame_capacity, uint8_t* d_out, uint64_t byte_capacity,
+                                      uint64_t* d_rec_off, int32_t* d_rec_status, uint64_t* d_written, void* stream)
+{
+    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!bam::params_valid(params)) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    const bool moves = (params->flags & PGN_BAM_MOVES) != 0, bgzf = (params->flags & PGN_BAM_BGZF) != 0;
+    if (nreads) {
+        if (!d_read_ids || !d_read_bases || !d_read_status || !d_rec_status) return PGN_ERR_INVALID_ARG;
+        for (uint32_t k = 0; k < params->ntags; k++)
+            if (!params->d_tag[k]) return PGN_ERR_INVALID_ARG;
+        if (moves && !d_read_frames) return PGN_ERR_INVALID_ARG;
+    }
+    if (!d_rec_off || !d_written) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && !d_seq) return PGN_ERR_INVALID_ARG;
+    if (moves && frame_capacity && !d_codes) return PGN_ERR_INVALID_ARG;
+    if (byte_capacity && !d_out) return PGN_ERR_INVALID_ARG;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    if (nreads == 0) {
+        HIPCHK(hipMemsetAsync(d_rec_off, 0, sizeof(uint64_t), s));
+        HIPCHK(hipMemsetAsync(d_written, 0, 2 * sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    bam::Args a{};
+    a.nreads = nreads;
+    a.ids = d_read_ids;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.keep = d_keep;
+    a.seq = d_seq;
+    a.qual = d_qual;
+    a.baseCapacity = base_capacity;
+    a.readFrames = d_read_frames;
+    a.codes = d_codes;
+    a.frameBase = frame_base;
+    a.frameCapacity = frame_capacity;
+    a.out = d_out;
+    a.streamCapacity = bgzf ? bam::bgzf_stream_capacity(byte_capacity) : byte_capacity;
+    a.recOff = d_rec_off;
+    a.recStatus = d_rec_status;
+    a.written = d_written;
+    a.nblocks = (nreads + bam::kScanThreads - 1) / bam::kScanThreads;
+    a.ntiles = (a.streamCapacity + bam::kBlock - 1) / bam::kBlock;
+    a.crcSplit = bgzf && c->bamCrcSplit;
+    a.prm = *params;
+    const int rc = reserve(c, {{c->fqWork, (size_t)(a.nblocks + 1) * sizeof(uint64_t)}});
+    if (rc != PGN_OK) return rc;
+    a.blockSums = c->fqWork;
+    hipLaunchKernelGGL(bam::bam_len_kernel, dim3((unsigned)a.nblocks), dim3(bam::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    stitch::PlanArgs top{};  // the scan of the workgroups' totals is the stitch plan's
+    top.blockSums = a.blockSums;
+    top.nblocks = a.nblocks;
+    hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, top);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(bam::bam_offset_kernel, dim3((unsigned)a.nblocks), dim3(bam::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (a.ntiles) {
+        // tiles behind the written records end at once, so a capacity far above the stream costs little
+        const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, 1u << 24);
+        hipLaunchKernelGGL(bam::bam_write_kernel, dim3(grid), dim3(bam::kThreads), 0, s, a);
+        HIPCHK(hipGetLastError());
+        if (a.crcSplit) {
+            hipLaunchKernelGGL(bam::bgzf_crc_kernel, dim3(grid), dim3(bam::kThreads), 0, s, a);
+            HIPCHK(hipGetLastError());
+        }
     }
     return PGN_OK;
 }

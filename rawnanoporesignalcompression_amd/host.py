@@ -566,3 +566,140 @@ def fastq_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=
             at += len(rec)
         rec_off[r + 1] = at
     return b"".join(text), rec_off, rec_status
+
+
+# ---- BAM records: unaligned records, the move table and BGZF framing ------------------------------------------------
+BGZF_BLOCK_BYTES = _native.PGN_BGZF_BLOCK_BYTES      # payload bytes of a block, htslib's 0xff00
+BGZF_OVERHEAD = 31                                   # 18 header, 5 stored-deflate prefix, 8 trailer
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+_BGZF_HEAD = bytes.fromhex("1f8b08040000000000ff060042430200")
+_BAM_NIBBLE = np.full(256, 15, np.uint8)
+for _i, _c in enumerate(b"=ACMGRSVTWYHKDBN"):
+    _BAM_NIBBLE[_c] = _i
+    _BAM_NIBBLE[ord(chr(_c).lower())] = _i
+
+
+def bam_bound(nreads, nbases, ntags=0, nframes=None) -> int:
+    """Stream bytes that hold the records of ``nreads`` reads with ``nbases`` bases in all, ``ntags`` tags each
+    and, with a move table, ``nframes`` frames in all: ``nreads * (74 + 7 * ntags) + nbases + nbases // 2``, plus
+    ``9 * nreads + nframes`` (the packed bases of a read round up by at most half a byte)."""
+    n = int(nreads) * (74 + 7 * int(ntags)) + int(nbases) + int(nbases) // 2
+    return n if nframes is None else n + 9 * int(nreads) + int(nframes)
+
+
+def bgzf_bound(nbytes) -> int:
+    """File bytes of ``nbytes`` stream bytes in BGZF blocks: ``nbytes + 31 * ceil(nbytes / 65280)``."""
+    nbytes = int(nbytes)
+    return nbytes + BGZF_OVERHEAD * (-(-nbytes // BGZF_BLOCK_BYTES))
+
+
+def bgzf_stream_capacity(byte_capacity) -> int:
+    """The largest ``S`` with ``bgzf_bound(S) <= byte_capacity``."""
+    q, rem = divmod(int(byte_capacity), BGZF_BLOCK_BYTES + BGZF_OVERHEAD)
+    return q * BGZF_BLOCK_BYTES + max(rem - BGZF_OVERHEAD, 0)
+
+
+def bgzf_blocks_signal(data) -> bytes:
+    """``data`` cut every 65,280 bytes into BGZF blocks that each hold one stored deflate block: the 18-byte
+    header with ``BSIZE = n + 30``, ``01 n ~n``, the ``n`` payload bytes, ``zlib.crc32`` of them and ``n``.  No
+    byte for no data, and no end-of-file marker (:data:`BGZF_EOF`)."""
+    import struct
+    import zlib
+
+    data = bytes(data)
+    out = []
+    for at in range(0, len(data), BGZF_BLOCK_BYTES):
+        p = data[at:at + BGZF_BLOCK_BYTES]
+        n = len(p)
+        out += [_BGZF_HEAD, struct.pack("<HBHH", n + 30, 1, n, n ^ 0xFFFF), p, struct.pack("<II", zlib.crc32(p), n)]
+    return b"".join(out)
+
+
+def bam_header(text=None) -> bytes:
+    """The BAM header of a file without references: ``BAM\\1``, ``l_text``, the text (default
+    ``@HD\\tVN:1.6\\tSO:unknown\\n``) and ``n_ref = 0``."""
+    import struct
+
+    text = b"@HD\tVN:1.6\tSO:unknown\n" if text is None else (text.encode() if isinstance(text, str) else bytes(text))
+    return b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", 0)
+
+
+def _bam_moves(moves):
+    """``(codes, read_frames, stride, frame_base)`` of a record call's ``moves``, checked."""
+    if len(moves) not in (3, 4):
+        raise ValueError("moves is (codes, read_frames, stride) or (codes, read_frames, stride, frame_base)")
+    stride, base = int(moves[2]), int(moves[3]) if len(moves) == 4 else 0
+    if not 1 <= stride <= 127:
+        raise ValueError("the stride is 1..127")
+    if base < 0:
+        raise ValueError("frame_base is not negative")
+    return moves[0], moves[1], stride, base
+
+
+def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=None, reverse=False, moves=None,
+                       base_capacity=None, byte_capacity=None, bgzf=False):
+    """The unaligned BAM records of a batch on the host (include/pgnano_hip.h, the rule of
+    pgn_bam_records_device).  A read is kept as in :func:`fastq_records_signal`; with ``moves`` = ``(codes,
+    read_frames, stride[, frame_base])`` its frames must also lie inside ``[frame_base, frame_base + len(codes))``
+    and number fewer than 2^31, else it has no record and status 10.  ``qual`` None writes ``0xFF`` qualities.
+    Returns ``(stream, rec_off, rec_status, written)``: the written records end to end, the scan of all lengths
+    (uint64, reads + 1), the statuses and ``[stream bytes, file bytes]``.  ``byte_capacity`` is that of the output
+    buffer: with ``bgzf`` the stream's capacity is :func:`bgzf_stream_capacity` of it, and the file's bytes are
+    ``bgzf_blocks_signal(stream)``."""
+    import struct
+
+    ids = np.asarray(read_ids, dtype=np.uint8).reshape(-1, 16)
+    seq = np.asarray(seq, dtype=np.uint8).reshape(-1)
+    qual = None if qual is None else np.asarray(qual, dtype=np.uint8).reshape(-1)
+    cap = len(seq) if base_capacity is None else int(base_capacity)
+    ranges = _read_ranges(read_bases, status, cap)
+    n = len(ranges)
+    if len(ids) != n:
+        raise ValueError("read_ids must hold 16 bytes per read")
+    cols = _fastq_tags(tags, n)
+    keep = None if keep is None else np.asarray(keep).reshape(-1)
+    if moves is not None:
+        codes, rf, stride, fbase = _bam_moves(moves)
+        codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+        rf = [int(v) for v in np.asarray(rf).reshape(-1)]
+        if len(rf) != n + 1:
+            raise ValueError("read_frames must hold one entry more than status")
+    limit = None if byte_capacity is None else (bgzf_stream_capacity(byte_capacity) if bgzf else int(byte_capacity))
+    hexd = "0123456789abcdef"
+    rec_off, rec_status = np.zeros(n + 1, np.uint64), np.asarray(status).astype(np.int32).reshape(-1).copy()
+    out, at, W = [], 0, 0
+    for r, (b0, m) in enumerate(ranges):
+        if m and (keep is None or keep[r] != 0):
+            mv = b""
+            if moves is not None:
+                f0, f1 = rf[r], rf[r + 1]
+                if not (fbase <= f0 <= f1 <= fbase + len(codes) and f1 - f0 < 2 ** 31):
+                    rec_status[r] = _native.PGN_ERR_INVALID_ARG
+                    rec_off[r + 1] = at
+                    continue
+                mv = b"mvBc" + struct.pack("<Ib", 1 + f1 - f0, stride) + ((codes[f0 - fbase:f1 - fbase] >> 7) & 1).tobytes()
+            h = "".join(hexd[b >> 4] + hexd[b & 15] for b in ids[r].tolist())
+            name = "-".join((h[:8], h[8:12], h[12:16], h[16:20], h[20:])).encode() + b"\0"
+            s = seq[b0:b0 + m][::-1] if reverse else seq[b0:b0 + m]
+            nib = np.concatenate([_BAM_NIBBLE[s], np.zeros(m & 1, np.uint8)])
+            packed = ((nib[0::2] << 4) | nib[1::2]).astype(np.uint8).tobytes()
+            if qual is None:
+                q = b"\xff" * m
+            else:
+                q = qual[b0:b0 + m][::-1] if reverse else qual[b0:b0 + m]
+                q = (np.clip(q, 33, 126) - 33).astype(np.uint8).tobytes()
+            body = struct.pack("<iiBBHHHIiii", -1, -1, 37, 0, 4680, 0, 4, m, -1, -1, 0) + name + packed + q
+            for tname, v in cols:
+                body += tname + b"I" + struct.pack("<I", int(v[r]))
+            body += mv
+            rec = struct.pack("<I", len(body)) + body
+            fits = limit is None or at + len(rec) <= limit
+            rec_status[r] = _native.PGN_OK if fits else _native.PGN_ERR_DST_TOO_SMALL
+            if fits:
+                out.append(rec)
+            at += len(rec)
+            if fits:
+                W = at
+        rec_off[r + 1] = at
+    written = np.array([W, bgzf_bound(W) if bgzf else W], np.uint64)
+    return b"".join(out), rec_off, rec_status, written
