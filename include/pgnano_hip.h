@@ -840,7 +840,7 @@ int pgn_base_qual_device(pgn_ctx *ctx, const pgn_qual_params *params, size_t nre
  *
  * Not covered: SAM/uBAM output, and the move-table tag; a float qs:f: tag; compression of the text; pass and fail
  * files from one call; records for the CTC path's bases without qualities; signed or 64-bit tag values; splitting
- * of reads. */
+ * of reads.  The text leaves compressed through pgn_bgzf_deflate_device ("BGZF deflate" below). */
 #define PGN_READ_QUAL_TILE_BASES 4096u
 #define PGN_FASTQ_TILE_BYTES 16384u
 #define PGN_FASTQ_MAX_TAGS 8u
@@ -931,7 +931,7 @@ int pgn_fastq_records_device(pgn_ctx *ctx, const pgn_fastq_params *params, size_
  *
  * Not covered: deflate compression (every block holds a stored deflate block, as `samtools view -u` writes);
  * aligned records and reference headers; qs:f and other non-uint32 tags; a reversed move table; SAM text; BGZF
- * framing of other buffers. */
+ * framing of other buffers.  Both are pgn_bgzf_deflate_device's ("BGZF deflate" below), which reads the raw layout. */
 #define PGN_BAM_MAX_TAGS 8u
 #define PGN_BAM_REVERSE 1u
 #define PGN_BAM_MOVES 2u
@@ -954,6 +954,68 @@ int pgn_bam_records_device(pgn_ctx *ctx, const pgn_bam_params *params, size_t nr
                            const uint64_t *d_read_frames, const uint8_t *d_codes, uint64_t frame_base,
                            uint64_t frame_capacity, uint8_t *d_out, uint64_t byte_capacity, uint64_t *d_rec_off,
                            int32_t *d_rec_status, uint64_t *d_written, void *stream);
+
+/* ---- BGZF deflate -------------------------------------------------------------------------------------------
+ * Any device byte stream in BGZF blocks that each hold one Huffman-only dynamic deflate block, or a stored block
+ * where that is not smaller, packed end to end: the raw records of pgn_bam_records_device (without PGN_BAM_BGZF),
+ * the text of pgn_fastq_records_device, anything else.
+ *   ... -> pgn_bam_records_device (raw) | pgn_fastq_records_device -> pgn_bgzf_deflate_device
+ * The container is SAMv1 section 4.1's and the bit stream RFC 1951's; which of the many valid streams is written no
+ * outside program defines, so this text does.  Integers and bits alone: the tolerance is zero.
+ *
+ * The stream.  Its length is W = min(*d_nbytes, src_capacity), and W = src_capacity with d_nbytes == NULL.  It is cut
+ * every PGN_BGZF_BLOCK_BYTES = 65,280 bytes: block k < nblocks = ceil(W / 65280) has a payload p of n bytes, 1 <= n <=
+ * 65280.
+ * The file bytes of block k: the 16 header bytes of "BAM records", BSIZE as u16 = the block's total length minus 1,
+ * the deflate bytes, CRC32(p) as u32, n as u32.
+ * The deflate bytes are the dynamic block below if its byte length is < n + 5, else the stored block 01 n ~n p (n and
+ * ~n as u16).  A tie stores.
+ * The dynamic block.  Bits fill each byte from bit 0 upwards.
+ *   Counts: cnt[s] for s < 256 is the number of payload bytes equal to s; cnt[256] = 1, the end-of-block symbol.
+ *   ll = lengths(cnt, 15) over the 257 symbols.
+ *   Header bits, in this order: BFINAL = 1 in 1 bit; BTYPE = 2 in 2 bits; HLIT = 0 in 5 bits (257 codes); HDIST = 1 in
+ *   5 bits (two distance codes, both of length 1 and never used, as zlib writes them, so every inflater reads it);
+ *   HCLEN - 4 in 4 bits.
+ *   The length sequence has 259 entries: ll[0..256], 1, 1.  It is cut into maximal runs of equal values over the whole
+ *   sequence (a run may join ll[256] and the two trailing ones).
+ *   A run of r zeros: while r >= 11, symbol 18 with t = min(r, 138), extra value t - 11 in 7 bits, r -= t; then if
+ *   r >= 3, symbol 17 with r - 3 in 3 bits; otherwise r literal zeros.
+ *   A run of r values v > 0: v once, r -= 1; while r >= 3, symbol 16 with t = min(r, 6), extra value t - 3 in 2 bits,
+ *   r -= t; then r literal v.
+ *   cl = lengths(histogram of those symbols, 7) over the 19 code-length symbols.
+ *   HCLEN is the position of the last non-zero cl in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, plus
+ *   one, and at least 4; that many lengths follow, 3 bits each.  Then the symbols, each followed by its extra bits.
+ *   Then the n literals' codes and the code of symbol 256.
+ *   Codes are canonical (RFC 1951 section 3.2.2) and written from their most significant bit; extra bits from their
+ *   least significant bit.  The last byte is padded with zeros.
+ * lengths(cnt, L).  The used symbols (cnt > 0), sorted by (cnt, symbol) ascending, are the leaf queue; internal nodes
+ * queue in creation order.  Each step takes the two smallest weights from the fronts of the two queues, the leaf where
+ * its weight is <= the internal node's; the new node's weight is their sum.  A symbol's length is its leaf's depth.
+ * One used symbol alone gets length 1.  If the largest length exceeds L, the limiter:
+ *   1. every length above L becomes L; 2. K = sum 2^(L - len);
+ *   3. while K > 2^L: among the used symbols with len < L take the longest length, then the smallest count, then the
+ *      largest symbol, and give it one more bit;
+ *   4. D = 2^L - K; 5. while D > 0: among the used symbols with len > 1 and 2^(L - len) <= D take the largest count,
+ *      then the smallest symbol, subtract that 2^(L - len) from D and take one bit from the symbol.
+ * Layout and capacity.  d_blk_off[0 .. ntiles], ntiles = ceil(src_capacity / 65280), is the exclusive scan of the
+ * blocks' file lengths and always holds the full counts; entries above nblocks repeat the total.  Block k is written
+ * iff blk_off[k + 1] <= byte_capacity, so the written blocks are a prefix; call their number kw.  d_written[0] =
+ * min(W, 65280 * kw) is the stream bytes consumed, d_written[1] = blk_off[kw].  There are no partial blocks.  Nothing
+ * at or beyond d_out + d_written[1] is touched, and nothing in front of d_out; d_src and d_out may have any alignment.
+ * bgzf_bound(src_capacity) always suffices, because a block is never longer than its stored form.  W == 0 writes no
+ * block.  The blocks of one call are a self-contained run, so batches concatenate in front of the 28-byte end marker.
+ * Three kernels: a workgroup per block counts, checksums and builds both codes (the plan); the scan of the lengths;
+ * a workgroup per block writes the bits into an image in LDS and stores it (the pack).  No match search.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx; flags != 0; with src_capacity > 0 a NULL d_src; a
+ * NULL d_blk_off or d_written; with byte_capacity > 0 a NULL d_out; src_capacity >= 2^48.  src_capacity == 0 writes
+ * blk_off[0] = 0 and d_written = {0, 0} only.  Asynchronous on `stream`, no host wait; the scratch is 1,568 bytes per
+ * block of src_capacity (the header's bits, the 257 codes and the CRC between the plan and the pack).
+ *
+ * Not covered: a match search, so the output is Huffman only; several deflate blocks per BGZF block; fixed-Huffman
+ * blocks; a .gzi or .bai index from blk_off; fusing into the record writers; decompression. */
+int pgn_bgzf_deflate_device(pgn_ctx *ctx, uint32_t flags /* 0 */, const uint8_t *d_src, uint64_t src_capacity,
+                            const uint64_t *d_nbytes /* may be NULL */, uint8_t *d_out, uint64_t byte_capacity,
+                            uint64_t *d_blk_off, uint64_t *d_written, void *stream);
 
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->

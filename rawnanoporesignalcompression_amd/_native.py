@@ -237,6 +237,8 @@ SIGNATURES = [
     ("pgn_bam_records_device", C.c_int,
      [_VP, C.POINTER(BamParams), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _U64P, _VP, C.c_uint64, C.c_uint64,
       _VP, C.c_uint64, _U64P, _I32P, _U64P, _VP]),
+    ("pgn_bgzf_deflate_device", C.c_int,
+     [_VP, C.c_uint32, _VP, C.c_uint64, _U64P, _VP, C.c_uint64, _U64P, _U64P, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

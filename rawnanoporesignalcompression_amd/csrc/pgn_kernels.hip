@@ -26,6 +26,7 @@
 #include "pgn_qual.h"
 #include "pgn_fastq.h"
 #include "pgn_bam.h"
+#include "pgn_deflate.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2165,6 +2166,10 @@ struct pgn_ctx {
     // the same totals and their sum.  PGN_BAM_CRC=split moves the BGZF checksum into a kernel of its own
     // (measurements only: the bytes are the same)
     DevBuf<uint64_t> fqWork{bufs};
+    // pgn_bgzf_deflate_device: a deflate::BlockPlan per 65,280 stream bytes, written by the plan kernel of every call.
+    // PGN_BGZF_KERNELS=plan | scan ends the call behind that kernel (measurements only: no block is written)
+    DevBuf<deflate::BlockPlan> bgzfPlans{bufs};
+    int bgzfKernels = 3;
     bool bamCrcSplit = false;
     uint64_t crfCap = crf::kDefaultScratch;
     int crfTrace = 0;  // 0 in the row's workgroup, 1 split, 2 none
@@ -2284,6 +2289,7 @@ static int ctx_init(pgn_ctx* c)
     if (const char* v = getenv("PGN_HUF_PRIO_LAST")) c->hufPrioLast = v[0] == '1';
     if (const char* v = getenv("PGN_CRF_TRACEBACK")) c->crfTrace = strcmp(v, "split") == 0 ? 1 : strcmp(v, "none") == 0 ? 2 : 0;
     if (const char* v = getenv("PGN_BAM_CRC")) c->bamCrcSplit = strcmp(v, "split") == 0;
+    if (const char* v = getenv("PGN_BGZF_KERNELS")) c->bgzfKernels = strcmp(v, "plan") == 0 ? 1 : strcmp(v, "scan") == 0 ? 2 : 3;
     if (const char* v = getenv("PGN_DEFER_TAIL_PLAIN")) { const long x = atol(v); if (x >= 0) c->deferTailPlain = (size_t)x; }
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const char* pe = getenv("PGN_PHASE_PROFILE");
@@ -4140,6 +4146,53 @@ extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, 
             HIPCHK(hipGetLastError());
         }
     }
+    return PGN_OK;
+}
+
+// ---- BGZF deflate (pgn_deflate.h) -----------------------------------------------------------------------------
+extern "C" int pgn_bgzf_deflate_device(pgn_ctx* c, uint32_t flags, const uint8_t* d_src, uint64_t src_capacity,
+                                       const uint64_t* d_nbytes, uint8_t* d_out, uint64_t byte_capacity,
+                                       uint64_t* d_blk_off, uint64_t* d_written, void* stream)
+{
+    if (!c) return PGN_ERR_INVALID_ARG;
+    if (flags) return PGN_ERR_INVALID_ARG;
+    if (src_capacity && !d_src) return PGN_ERR_INVALID_ARG;
+    if (!d_blk_off || !d_written) return PGN_ERR_INVALID_ARG;
+    if (byte_capacity && !d_out) return PGN_ERR_INVALID_ARG;
+    if (src_capacity >> 48) return PGN_ERR_INVALID_ARG;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    if (src_capacity == 0) {
+        HIPCHK(hipMemsetAsync(d_blk_off, 0, sizeof(uint64_t), s));
+        HIPCHK(hipMemsetAsync(d_written, 0, 2 * sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    deflate::Args a{};
+    a.src = d_src;
+    a.srcCapacity = src_capacity;
+    a.nbytes = d_nbytes;
+    a.out = d_out;
+    a.byteCapacity = byte_capacity;
+    a.blkOff = d_blk_off;
+    a.written = d_written;
+    a.ntiles = (src_capacity + deflate::kBlock - 1) / deflate::kBlock;
+    const int rc = reserve(c, {{c->bgzfPlans, (size_t)a.ntiles * sizeof(deflate::BlockPlan)}});
+    if (rc != PGN_OK) return rc;
+    a.plans = c->bgzfPlans;
+    // tiles behind the stream's end finish at once, so a capacity far above *d_nbytes costs little
+    const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, 1u << 24);
+    hipLaunchKernelGGL(deflate::deflate_plan_kernel, dim3(grid), dim3(deflate::kThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    if (c->bgzfKernels < 2) return PGN_OK;
+    stitch::PlanArgs top{};  // the scan of the blocks' lengths is the stitch plan's
+    top.blockSums = d_blk_off;
+    top.nblocks = a.ntiles;
+    hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, top);
+    HIPCHK(hipGetLastError());
+    if (c->bgzfKernels < 3) return PGN_OK;
+    hipLaunchKernelGGL(deflate::deflate_pack_kernel, dim3(grid), dim3(deflate::kThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
     return PGN_OK;
 }
 

@@ -703,3 +703,185 @@ def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=No
         rec_off[r + 1] = at
     written = np.array([W, bgzf_bound(W) if bgzf else W], np.uint64)
     return b"".join(out), rec_off, rec_status, written
+
+
+# ---- BGZF deflate: one Huffman-only dynamic deflate block per BGZF block, or a stored one ---------------------------
+_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+
+
+def deflate_lengths_signal(cnt, limit):
+    """Code lengths of the symbols with the counts ``cnt``, none above ``limit`` (include/pgnano_hip.h, "BGZF
+    deflate", ``lengths`` and the limiter): a two-queue Huffman construction over the used symbols sorted by
+    ``(count, symbol)``, a lone symbol at length 1, and lengths above the limit repaired to a complete code."""
+    cnt = [int(c) for c in cnt]
+    L = int(limit)
+    out = [0] * len(cnt)
+    leaves = sorted((c, s) for s, c in enumerate(cnt) if c > 0)
+    m = len(leaves)
+    if m == 0:
+        return out
+    if m == 1:
+        out[leaves[0][1]] = 1
+        return out
+    w = [c for c, _ in leaves] + [0] * (m - 1)
+    parent = [0] * (2 * m - 1)
+    li, ii = 0, m
+    for nxt in range(m, 2 * m - 1):
+        pair = []
+        for _ in range(2):
+            if li < m and (ii >= nxt or w[li] <= w[ii]):
+                pair.append(li)
+                li += 1
+            else:
+                pair.append(ii)
+                ii += 1
+        w[nxt] = w[pair[0]] + w[pair[1]]
+        parent[pair[0]] = parent[pair[1]] = nxt
+    depth = [0] * (2 * m - 1)
+    for i in range(2 * m - 3, -1, -1):
+        depth[i] = depth[parent[i]] + 1
+    for i, (_, s) in enumerate(leaves):
+        out[s] = depth[i]
+    if max(out) <= L:
+        return out
+    used = [s for _, s in leaves]
+    for s in used:
+        out[s] = min(out[s], L)
+    K = sum(1 << (L - out[s]) for s in used)
+    while K > 1 << L:
+        s = max((s for s in used if out[s] < L), key=lambda s: (out[s], -cnt[s], s))
+        K -= 1 << (L - out[s] - 1)
+        out[s] += 1
+    D = (1 << L) - K
+    while D > 0:
+        s = max((s for s in used if out[s] > 1 and 1 << (L - out[s]) <= D), key=lambda s: (cnt[s], -s))
+        D -= 1 << (L - out[s])
+        out[s] -= 1
+    return out
+
+
+def _canonical_codes(lens):
+    """RFC 1951 section 3.2.2: the code of every symbol with a length, as an integer read from its most significant bit."""
+    top = max(lens)
+    count = [0] * (top + 2)
+    for v in lens:
+        count[v] += 1
+    count[0] = 0
+    nxt, code = [0] * (top + 2), 0
+    for b in range(1, top + 1):
+        code = (code + count[b - 1]) << 1
+        nxt[b] = code
+    codes = [0] * len(lens)
+    for s, v in enumerate(lens):
+        if v:
+            codes[s] = nxt[v]
+            nxt[v] += 1
+    return codes
+
+
+def _length_symbols(ll):
+    """The length sequence ``ll[0..256], 1, 1`` in code-length symbols by the rule's runs: ``(symbol, extra value,
+    extra bits)`` each."""
+    seq = list(ll) + [1, 1]
+    syms = []
+    at = 0
+    while at < len(seq):
+        v, r = seq[at], 1
+        while at + r < len(seq) and seq[at + r] == v:
+            r += 1
+        at += r
+        if v == 0:
+            while r >= 11:
+                t = min(r, 138)
+                syms.append((18, t - 11, 7))
+                r -= t
+            if r >= 3:
+                syms.append((17, r - 3, 3))
+            else:
+                syms += [(0, 0, 0)] * r
+        else:
+            syms.append((v, 0, 0))
+            r -= 1
+            while r >= 3:
+                t = min(r, 6)
+                syms.append((16, t - 3, 2))
+                r -= t
+            syms += [(v, 0, 0)] * r
+    return syms
+
+
+def _deflate_dynamic(p):
+    """The dynamic block of the rule for the payload ``p`` (1 to 65,280 bytes)."""
+    cnt = np.bincount(np.frombuffer(p, np.uint8), minlength=256).tolist() + [1]
+    ll = deflate_lengths_signal(cnt, 15)
+    syms = _length_symbols(ll)
+    clcnt = [0] * 19
+    for s, _, _ in syms:
+        clcnt[s] += 1
+    cl = deflate_lengths_signal(clcnt, 7)
+    hclen = max(4, max(i + 1 for i, s in enumerate(_CL_ORDER) if cl[s]))
+    acc = nbits = 0
+
+    def put(value, bits):
+        nonlocal acc, nbits
+        acc |= value << nbits
+        nbits += bits
+
+    def put_code(code, bits):
+        put(int(format(code, f"0{bits}b")[::-1], 2), bits)
+
+    put(1, 1), put(2, 2), put(0, 5), put(1, 5), put(hclen - 4, 4)
+    for s in _CL_ORDER[:hclen]:
+        put(cl[s], 3)
+    clcode = _canonical_codes(cl)
+    for s, extra, ebits in syms:
+        put_code(clcode[s], cl[s])
+        put(extra, ebits)
+    # the literals: every symbol's code reversed once, then the payload's bits end to end
+    code = _canonical_codes(ll)
+    rev = [int(format(code[s], f"0{ll[s]}b")[::-1], 2) if ll[s] else 0 for s in range(257)]
+    lit = np.frombuffer(p, np.uint8)
+    bits_of, rev_of = np.asarray(ll, np.int64)[lit], np.asarray(rev, np.int64)[lit]
+    at = nbits + np.concatenate([[0], np.cumsum(bits_of)])
+    end = int(at[-1]) + ll[256]
+    bits = np.zeros(end, np.uint8)
+    bits[:nbits] = [(acc >> i) & 1 for i in range(nbits)]
+    for k in range(15):
+        has = bits_of > k
+        bits[at[:-1][has] + k] = (rev_of[has] >> k) & 1
+    bits[int(at[-1]):] = [(rev[256] >> i) & 1 for i in range(ll[256])]
+    return np.packbits(bits, bitorder="little").tobytes()
+
+
+def deflate_block_signal(payload) -> bytes:
+    """The deflate bytes of one BGZF block's payload (1 to 65,280 bytes) by the rule of pgn_bgzf_deflate_device:
+    the Huffman-only dynamic block where it is shorter than the stored block ``01 n ~n payload``, else that."""
+    import struct
+
+    p = bytes(payload)
+    n = len(p)
+    if not 1 <= n <= BGZF_BLOCK_BYTES:
+        raise ValueError("a block's payload is 1 to 65,280 bytes")
+    dyn = _deflate_dynamic(p)
+    return dyn if len(dyn) < n + 5 else struct.pack("<BHH", 1, n, n ^ 0xFFFF) + p
+
+
+def bgzf_deflate_signal(data, byte_capacity=None):
+    """``data`` cut every 65,280 bytes into BGZF blocks of :func:`deflate_block_signal`, packed end to end
+    (include/pgnano_hip.h, the rule of pgn_bgzf_deflate_device).  Returns ``(file bytes, blk_off, written)``:
+    the whole blocks that ``byte_capacity`` holds (None: all), the scan of all blocks' file lengths (uint64,
+    blocks + 1) and ``[stream bytes consumed, file bytes written]``.  No end-of-file marker."""
+    import struct
+    import zlib
+
+    data = bytes(data)
+    blocks = []
+    for at in range(0, len(data), BGZF_BLOCK_BYTES):
+        p = data[at:at + BGZF_BLOCK_BYTES]
+        body = deflate_block_signal(p)
+        blocks.append(_BGZF_HEAD + struct.pack("<H", len(body) + 25) + body + struct.pack("<II", zlib.crc32(p), len(p)))
+    blk_off = np.zeros(len(blocks) + 1, np.uint64)
+    blk_off[1:] = np.cumsum([len(b) for b in blocks], dtype=np.uint64)
+    kw = len(blocks) if byte_capacity is None else int(np.searchsorted(blk_off, int(byte_capacity), "right")) - 1
+    written = np.array([min(len(data), BGZF_BLOCK_BYTES * kw), int(blk_off[kw])], np.uint64)
+    return b"".join(blocks[:kw]), blk_off, written

@@ -1,0 +1,111 @@
+"""BGZF deflate on the GPU (pgn_bgzf_deflate_device through bgzf.bgzf_deflate), bit for bit against
+bgzf_deflate_signal on the cases of tests/_bgzf_cases.py: records, text, runs of zeros, single bytes, incompressible
+bytes, codes that need either limiter, both sides of the stored/dynamic break-even, every stream length around a
+block, every alignment of the source and the output, every kind of capacity and of ``nbytes``.  Every byte that no
+written block owns keeps its sentinel, in front of and behind ``out`` too.
+"""
+import gzip
+
+import numpy as np
+import pytest
+
+import _bgzf_cases as K
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL, FRONT, BACK = 0xA5, 64, 80
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return {c.name: c for c in K.deflate_cases()}
+
+
+def run(codec, c, stream=None, nbytes_as_int=False):
+    """One call from a view of one buffer into a view of a sentinel-filled one; everything compared."""
+    import torch
+
+    from rawnanoporesignalcompression_amd import bgzf
+
+    dev = "cuda:0"
+    n = len(c.data)
+    src_buf = torch.full((16 + n + 16,), 0x5A, dtype=torch.uint8, device=dev)
+    assert src_buf.data_ptr() % 16 == 0
+    src = src_buf[c.src_offset:c.src_offset + n]
+    if n:
+        src.copy_(torch.from_numpy(np.frombuffer(c.data, np.uint8).copy()))
+    cap = c.capacity
+    buf = torch.full((FRONT + c.out_offset + cap + BACK,), SENTINEL, dtype=torch.uint8, device=dev)
+    assert buf.data_ptr() % 16 == 0
+    out = buf[FRONT + c.out_offset:FRONT + c.out_offset + cap]
+    nbytes = c.nbytes
+    if nbytes is not None and not nbytes_as_int:
+        nbytes = torch.tensor([nbytes], dtype=torch.int64, device=dev)
+    got = bgzf.bgzf_deflate(codec, src, nbytes, out=out, stream=stream)
+    torch.cuda.synchronize()
+    data, off, written = c.expected()
+    assert got.data.data_ptr() == out.data_ptr()
+    if nbytes_as_int:                                       # the binding cut the source: fewer tiles, the same scan
+        off = off[:-(-min(c.nbytes, n) // K.B) + 1]
+    assert np.array_equal(got.blk_off.cpu().numpy().view(np.uint64), off), c.name
+    assert np.array_equal(got.written.cpu().numpy().view(np.uint64), written), c.name
+    have = buf.cpu().numpy()
+    at = FRONT + c.out_offset
+    if have[at:at + len(data)].tobytes() != data:
+        g = have[at:at + len(data)]
+        bad = np.flatnonzero(g != np.frombuffer(data, np.uint8))
+        raise AssertionError(f"{c.name}: {len(bad)} bytes differ, the first at {bad[:8].tolist()}")
+    # the guard bytes, and with them every byte of a block that was not written
+    assert (have[:at] == SENTINEL).all() and (have[at + len(data):] == SENTINEL).all(), c.name
+    assert got.tobytes() == data
+    assert src_buf.cpu().numpy()[c.src_offset:c.src_offset + n].tobytes() == c.data
+    return got
+
+
+@pytest.mark.parametrize("name", [c.name for c in K.deflate_cases()])
+def test_blocks(codec, cases, name):
+    run(codec, cases[name])
+
+
+def test_nothing_to_write_leaves_out_untouched(codec, cases):
+    for name in ("w-0", "nbytes-zero", "capacity-zero", "capacity-first-short"):
+        got = run(codec, cases[name])
+        assert not got.written.cpu().numpy().any() and got.tobytes() == b""
+
+
+def test_default_out_int_nbytes_and_tobytes(codec, cases):
+    """Without ``out`` the call sizes it by bgzf_bound; an int ``nbytes`` cuts the source on the host."""
+    import torch
+
+    from rawnanoporesignalcompression_amd import bgzf
+
+    c = cases["fastq"]
+    src = torch.from_numpy(np.frombuffer(c.data, np.uint8).copy()).to("cuda:0")
+    got = bgzf.bgzf_deflate(codec, src)
+    assert int(got.data.numel()) == bgzf.bgzf_bound(len(c.data)) and got.tobytes() == c.expected()[0]
+    assert gzip.decompress(got.tobytes()) == c.data
+    part = bgzf.bgzf_deflate(codec, src, K.B + 5)
+    assert int(part.blk_off.numel()) == 3 and gzip.decompress(part.tobytes()) == c.data[:K.B + 5]
+    run(codec, cases["nbytes-below"], nbytes_as_int=True)
+    for bad in (dict(data=src.cpu()), dict(data=src.to(torch.int8)), dict(data=src.reshape(1, -1)), dict(data=src[::2]),
+                dict(nbytes=-1), dict(nbytes=torch.tensor([5], device="cuda:0", dtype=torch.int32)),
+                dict(nbytes=torch.tensor([5, 6], device="cuda:0")), dict(nbytes=torch.tensor([5])),
+                dict(out=torch.empty(10, dtype=torch.int8, device="cuda:0")), dict(out=torch.empty(10, dtype=torch.uint8))):
+        args = dict(data=src, nbytes=None)
+        args.update({k: v for k, v in bad.items() if k in args})
+        with pytest.raises(ValueError):
+            bgzf.bgzf_deflate(codec, args["data"], args["nbytes"], **{k: v for k, v in bad.items() if k not in args})
+
+
+def test_repeated_calls_and_a_callers_stream(codec, cases):
+    """A large call, then small ones on the same context (the scratch of the first is stale for them), then some on
+    a caller's stream."""
+    import torch
+
+    for name in ("bam", "tiny-1", "break-even-1", "w-65281", "limited-header"):
+        run(codec, cases[name])
+    s = torch.cuda.Stream()
+    run(codec, cases["w-196617"], stream=s.cuda_stream)
+    run(codec, cases["align-15-1"], stream=s.cuda_stream)
+    run(codec, cases["deep-histogram"], stream=s.cuda_stream)
+    run(codec, cases["bam"])
