@@ -18,6 +18,7 @@ import pytest
 
 import _bam_cases
 import _bgzf_cases as K
+from rawnanoporesignalcompression_amd import host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FN = "pgn_bgzf_deflate_device"
@@ -31,6 +32,11 @@ def _header(comments=False):
 @pytest.fixture(scope="module")
 def cases():
     return K.deflate_cases()
+
+
+@pytest.fixture(scope="module")
+def hazards():
+    return K.hazard_cases()
 
 
 # ---- surface -------------------------------------------------------------------------------------------------
@@ -110,7 +116,7 @@ def test_the_header_carries_the_rule():
 
 
 # ---- the model against zlib ----------------------------------------------------------------------------------------
-def test_every_case_inflates_and_is_laid_out(cases):
+def _inflates_and_is_laid_out(cases):
     for c in cases:
         data, off, written = c.expected()
         stream = c.data[:c.W]
@@ -133,6 +139,15 @@ def test_every_case_inflates_and_is_laid_out(cases):
         assert len(blocks) == nblocks or int(off[len(blocks) + 1]) > c.capacity, c.name
         from rawnanoporesignalcompression_amd.host import bgzf_bound
         assert int(off[-1]) <= bgzf_bound(c.W)
+
+
+def test_every_case_inflates_and_is_laid_out(cases):
+    _inflates_and_is_laid_out(cases)
+
+
+def test_every_hazard_case_inflates_and_is_laid_out(hazards):
+    _inflates_and_is_laid_out(hazards)
+    assert all(len(_bam_cases.parse_bgzf(c.expected()[0])) == 1 for c in hazards), "single blocks"
 
 
 def test_python_model_refusals():
@@ -212,6 +227,220 @@ def test_size_against_zlib_huffman_only(cases):
             theirs += len(z.compress(c.data[at:at + K.B]) + z.flush())
         print(f"{name}: {ours} deflate bytes, zlib Z_HUFFMAN_ONLY {theirs}, ratio {ours / theirs:.4f}")
         assert ours <= 1.02 * theirs, (name, ours, theirs)
+
+
+def test_hazard_sizes_against_zlib_huffman_only(hazards):
+    """The same guard on every hazard payload: zlib limits its lengths by another rule and may code a small payload
+    with the fixed code, so a rule that loses bits to either limiter or to its runs would show here."""
+    worst = 0.0
+    for p in sorted({c.data for c in hazards}, key=len):
+        ours = len(K.deflate_block_signal(p))
+        z = zlib.compressobj(9, zlib.DEFLATED, -15, 9, zlib.Z_HUFFMAN_ONLY)
+        theirs = len(z.compress(p) + z.flush())
+        worst = max(worst, ours / theirs)
+        assert ours <= 1.02 * theirs, (len(p), ours, theirs)
+    print(f"hazard payloads: the worst ratio to zlib Z_HUFFMAN_ONLY is {worst:.4f}")
+
+
+# ---- the hazard list: what it meets, and that it can fail ------------------------------------------------------------
+def test_the_hazard_list_meets_every_condition(hazards):
+    """The table of the conditions the limiter families exist for, counted from the traces, and the build time."""
+    labels = K.hazard_labels()
+    rows = [(f"L{L}:{k}", n) for L, q in K.LIMIT_QUOTA.items() for k, n in q.items()] + [("both-limiters", 1)]
+    print(f"hazard_cases(): {len(hazards)} cases built in {K.hazard_build_seconds():.2f} s")
+    for label, need in rows:
+        have = sorted(name for name, v in labels.items() if label in v)
+        print(f"  {label:24s} needs {need}, has {len(have):2d}: {' '.join(have)}")
+        assert len(have) >= need, label
+    by_name = {c.name: c for c in hazards}
+    both = by_name[next(n for n, v in labels.items() if "both-limiters" in v)]
+    t = K.trace_limiter(K.counts_of(both.data), 15)
+    assert t.depth >= 18 and K.trace_limiter(K.plan_of(both.data).clcnt, 7).needed
+    # a tie across groups: two tied symbols at least 64 apart; a tie with the end of block: 256 among byte values of count 1
+    assert any(max(x) - min(x) >= 64 for c in hazards if c.name.startswith("limit-")
+               for x in K.trace_limiter(K.counts_of(c.data), 15).ties)
+    eob = by_name[next(n for n, v in labels.items() if "L15:tie-with-eob" in v)]
+    cnt = K.counts_of(eob.data)
+    assert any(256 in x and len(x) > 1 and all(cnt[s] == 1 for s in x) for x in K.trace_limiter(cnt, 15).ties)
+    # the lists of the other families
+    names = [c.name for c in hazards]
+    for prefix, count in (("merge-tie", 2), ("zero-runs-", 4), ("nonzero-runs", 1), ("ones-into-distances", 1), ("hclen-", 2),
+                          ("pack-15-bits-and-1-bit", 1), ("pack-eob-across-words", 1), ("pack-n-", len(K.PACK_LENGTHS)),
+                          ("pack-out-", 16), ("pack-src-", 15)):
+        assert len([n for n in names if n.startswith(prefix)]) == count, prefix
+    assert sorted(len(c.data) for c in hazards if c.name.startswith("pack-n-")) == sorted(K.PACK_LENGTHS)
+    assert {c.out_offset for c in hazards if c.name.startswith("pack-out-")} == set(range(16))
+    assert {(c.src_offset, c.out_offset) for c in hazards if c.name.startswith("pack-src-")} == {(s, 7) for s in range(1, 16)}
+    assert {r for c in hazards if c.name.startswith("zero-runs-") for r in map(int, c.name.split("-")[2:])} == set(K.ZERO_RUNS)
+    assert K.hazard_build_seconds() < 10, "the seeded searches stay short"
+
+
+MUTANTS = ("p1-tie-largest-count", "p1-tie-smallest-symbol", "p2-tie-largest-symbol", "p2-smallest-count", "p2-skipped",
+           "merge-prefers-internal", "rank-ties-reversed", "cap-18-at-137", "cap-16-at-5", "17-from-4", "hclen-untrimmed")
+TIE_MUTANTS = MUTANTS[:3]
+
+
+def _mutant_lengths(cnt, L, m):
+    """deflate_lengths_signal again, with the one thing changed that ``m`` names (None: nothing)."""
+    cnt = [int(c) for c in cnt]
+    out = [0] * len(cnt)
+    leaves = sorted(((c, s) for s, c in enumerate(cnt) if c > 0), key=lambda x: (x[0], -x[1] if m == "rank-ties-reversed" else x[1]))
+    n = len(leaves)
+    if n == 0:
+        return out
+    if n == 1:
+        out[leaves[0][1]] = 1
+        return out
+    w = [c for c, _ in leaves] + [0] * (n - 1)
+    parent = [0] * (2 * n - 1)
+    li, ii = 0, n
+    for nxt in range(n, 2 * n - 1):
+        pair = []
+        for _ in range(2):
+            if li < n and (ii >= nxt or (w[li] < w[ii] if m == "merge-prefers-internal" else w[li] <= w[ii])):
+                pair.append(li)
+                li += 1
+            else:
+                pair.append(ii)
+                ii += 1
+        w[nxt] = w[pair[0]] + w[pair[1]]
+        parent[pair[0]] = parent[pair[1]] = nxt
+    depth = [0] * (2 * n - 1)
+    for i in range(2 * n - 3, -1, -1):
+        depth[i] = depth[parent[i]] + 1
+    for i, (_, s) in enumerate(leaves):
+        out[s] = depth[i]
+    if max(out) <= L:
+        return out
+    used = [s for _, s in leaves]
+    for s in used:
+        out[s] = min(out[s], L)
+    k1 = {"p1-tie-largest-count": lambda s: (out[s], cnt[s], s), "p1-tie-smallest-symbol": lambda s: (out[s], -cnt[s], -s)}
+    k2 = {"p2-tie-largest-symbol": lambda s: (cnt[s], s), "p2-smallest-count": lambda s: (-cnt[s], -s)}
+    Kr = sum(1 << (L - out[s]) for s in used)
+    while Kr > 1 << L:
+        s = max((s for s in used if out[s] < L), key=k1.get(m, lambda s: (out[s], -cnt[s], s)))
+        Kr -= 1 << (L - out[s] - 1)
+        out[s] += 1
+    D = 0 if m == "p2-skipped" else (1 << L) - Kr
+    while D > 0:
+        s = max((s for s in used if out[s] > 1 and 1 << (L - out[s]) <= D), key=k2.get(m, lambda s: (cnt[s], -s)))
+        D -= 1 << (L - out[s])
+        out[s] -= 1
+    return out
+
+
+def _mutant_symbols(ll, m):
+    """_length_symbols again, with the run rule that ``m`` names changed."""
+    cap18, cap16, min17 = (137 if m == "cap-18-at-137" else 138), (5 if m == "cap-16-at-5" else 6), (4 if m == "17-from-4" else 3)
+    seq = list(ll) + [1, 1]
+    syms, at = [], 0
+    while at < len(seq):
+        v, r = seq[at], 1
+        while at + r < len(seq) and seq[at + r] == v:
+            r += 1
+        at += r
+        if v == 0:
+            while r >= 11:
+                t = min(r, cap18)
+                syms.append((18, t - 11, 7))
+                r -= t
+            if r >= min17:
+                syms.append((17, r - 3, 3))
+            else:
+                syms += [(0, 0, 0)] * r
+        else:
+            syms.append((v, 0, 0))
+            r -= 1
+            while r >= 3:
+                t = min(r, cap16)
+                syms.append((16, t - 3, 2))
+                r -= t
+            syms += [(v, 0, 0)] * r
+    return syms
+
+
+def _mutant_plan(p, m):
+    ll = _mutant_lengths(K.counts_of(p), 15, m)
+    syms = _mutant_symbols(ll, m)
+    clcnt = [0] * 19
+    for s, _, _ in syms:
+        clcnt[s] += 1
+    cl = _mutant_lengths(clcnt, 7, m)
+    hclen = 19 if m == "hclen-untrimmed" else max(4, max(i + 1 for i, s in enumerate(host._CL_ORDER) if cl[s]))
+    return ll, syms, cl, hclen
+
+
+def _mutant_block(plan, p):
+    """The dynamic block of a plan: the bits of _deflate_dynamic, written apart from it."""
+    ll, syms, cl, hclen = plan
+    fields = [(1, 1), (2, 2), (0, 5), (1, 5), (hclen - 4, 4)] + [(cl[s], 3) for s in host._CL_ORDER[:hclen]]
+    clcode = host._canonical_codes(cl)
+
+    def msb_first(code, bits):
+        return int(format(code, f"0{bits}b")[::-1], 2) if bits else 0
+
+    for s, extra, ebits in syms:
+        fields += [(msb_first(clcode[s], cl[s]), cl[s]), (extra, ebits)]
+    code = host._canonical_codes(ll)
+    rev = np.array([msb_first(code[s], ll[s]) for s in range(257)], np.int64)
+    lens = np.asarray(ll, np.int64)
+    lit = np.concatenate([np.frombuffer(p, np.uint8).astype(np.int64), [256]])
+    head = [(v >> i) & 1 for v, n in fields for i in range(n)]
+    at = len(head) + np.concatenate([[0], np.cumsum(lens[lit])])
+    bits = np.zeros(int(at[-1]), np.uint8)
+    bits[:len(head)] = head
+    for k in range(15):
+        has = lens[lit] > k
+        bits[at[:-1][has] + k] = (rev[lit][has] >> k) & 1
+    return np.packbits(bits, bitorder="little").tobytes()
+
+
+def _blocks_of(cases):
+    """The distinct payloads of the cases' blocks."""
+    return {c.name + (f"[{k // K.B}]" if c.W > K.B else ""): c.data[k:min(k + K.B, c.W)]
+            for c in cases for k in range(0, c.W, K.B)}
+
+
+def test_mutants_of_the_rule_fail_on_the_hazard_cases(cases, hazards):
+    """Eleven copies of the rule with one thing changed each: every one writes, for at least one hazard case, a block
+    that differs from the model's and still is a deflate block of the payload.  zlib inflates ten of them; it
+    refuses a literal code that is not complete, so the block without the give-back loop is held to its lengths: no
+    longer than 15, the Kraft sum at most 1.  The cases of deflate_cases() meet no tie at the limit of 15 and one at
+    the limit of 7 (limited-header, in phase 1, between equal counts that only the symbol order separates): of the
+    three tie mutants they tell that one from the rule, there, and no other."""
+    seen = {}
+    payloads = {}
+    for c in hazards:
+        payloads.setdefault(c.data, c.name)
+    for p, name in payloads.items():
+        same = _mutant_plan(p, None)
+        assert same == (lambda pl: (pl.ll, pl.syms, pl.cl, pl.hclen))(K.plan_of(p)), name
+        model = host._deflate_dynamic(p)
+        assert _mutant_block(same, p) == model, name
+        for m in MUTANTS:
+            plan = _mutant_plan(p, m)
+            if plan == same:
+                continue
+            block = _mutant_block(plan, p)
+            assert block != model, (m, name)
+            if m == "p2-skipped":
+                assert max(plan[0]) <= 15 and sum(1 << (15 - v) for v in plan[0] if v) <= 1 << 15
+                assert sum(1 << (7 - v) for v in plan[2] if v) <= 1 << 7
+            else:
+                z = zlib.decompressobj(-15)
+                assert z.decompress(block) == p and z.eof and not z.unused_data, (m, name)
+            seen.setdefault(m, []).append(name)
+    for m in MUTANTS:
+        print(f"  {m:24s} fails on {len(seen.get(m, ())):2d}: {' '.join(seen.get(m, ()))}")
+        assert seen.get(m), f"no hazard case tells the mutant {m} from the rule"
+    old = _blocks_of(cases)
+    for m in TIE_MUTANTS:
+        told = [name for name, p in old.items() if p and _mutant_plan(p, m) != _mutant_plan(p, None)]
+        print(f"  deflate_cases() alone: {m} fails on {told}")
+        # at the limit of 15 nothing; at 7, limited-header meets one phase-1 tie, which only the symbol order decides
+        assert not [name for name, p in old.items() if p and _mutant_lengths(K.counts_of(p), 15, m) != K.plan_of(p).ll], m
+        assert told == (["limited-header"] if m == "p1-tie-smallest-symbol" else []), (m, told)
 
 
 def test_write_gz_and_write_bam(tmp_path, cases):

@@ -1,8 +1,22 @@
 """BGZF deflate on the GPU (pgn_bgzf_deflate_device through bgzf.bgzf_deflate), bit for bit against
-bgzf_deflate_signal on the cases of tests/_bgzf_cases.py: records, text, runs of zeros, single bytes, incompressible
-bytes, codes that need either limiter, both sides of the stored/dynamic break-even, every stream length around a
-block, every alignment of the source and the output, every kind of capacity and of ``nbytes``.  Every byte that no
-written block owns keeps its sentinel, in front of and behind ``out`` too.
+bgzf_deflate_signal on the two case lists of tests/_bgzf_cases.py.
+
+deflate_cases() is the call's surface: records, text, runs of zeros, single bytes, incompressible bytes, one code that
+needs the literal limiter and two that need the code-length limiter (none of the three meets a tie, a pick below
+L - 1 at the limit of 7, or the give-back loop at that limit), both sides of the stored/dynamic break-even, every
+stream length around a block, source and output at offsets 0, 1 and 15 of 16, every kind of capacity and of
+``nbytes``.
+
+hazard_cases() is the code construction's and the pack kernel's: histograms found by seeded search whose limiter, at
+15 and at 7, meets ties in either loop (within one lane's registers, across lanes, with the end-of-block symbol),
+picks below L - 1 and gives bits back, one block that needs both limiters, ties of the two-queue merge, zero runs of
+3, 10, 11, 138, 139, 148 and 149 and non-zero runs of 4, 7, 10 and 11, HCLEN 18 and 19, a thread's run of 64 codes of
+15 bits and one of 1 bit, an end-of-block code across two words of the image, payload lengths around the last whole
+run of 64 bytes, and one payload at all 16 alignments of the output and of the source.  Each condition is asserted on
+the CPU where the case is built; tests/test_bgzf_deflate_api.py shows that mutants of the rule fail on them.
+
+Every byte that no written block owns keeps its sentinel, in front of and behind ``out`` too.  Streams whose offsets
+pass 2^32 are tests/test_gpu_wide_streams.py's.
 """
 import gzip
 
@@ -65,6 +79,16 @@ def run(codec, c, stream=None, nbytes_as_int=False):
 @pytest.mark.parametrize("name", [c.name for c in K.deflate_cases()])
 def test_blocks(codec, cases, name):
     run(codec, cases[name])
+
+
+@pytest.fixture(scope="module")
+def hazards():
+    return {c.name: c for c in K.hazard_cases()}
+
+
+@pytest.mark.parametrize("name", [c.name for c in K.hazard_cases()])
+def test_hazard_blocks(codec, hazards, name):
+    run(codec, hazards[name])
 
 
 def test_nothing_to_write_leaves_out_untouched(codec, cases):
