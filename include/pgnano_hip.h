@@ -1017,6 +1017,125 @@ int pgn_bgzf_deflate_device(pgn_ctx *ctx, uint32_t flags /* 0 */, const uint8_t 
                             const uint64_t *d_nbytes /* may be NULL */, uint8_t *d_out, uint64_t byte_capacity,
                             uint64_t *d_blk_off, uint64_t *d_written, void *stream);
 
+/* ---- Adapters and barcodes ----------------------------------------------------------------------------------
+ * The step between "bases" and "records": where the adapter, primer and barcode sequences lie at the two ends of
+ * each read, which barcode the read carries, and the read cut to what lies between, with its qualities and its
+ * move table.
+ *   ... -> pgn_collapse_codes_device -> pgn_find_patterns_device -> pgn_classify_reads_device
+ *       -> pgn_trim_reads_device -> pgn_base_qual_device ... pgn_bam_records_device | pgn_fastq_records_device
+ * No outside program defines the rule, so this text does.  Integers and bytes alone: the tolerance is zero.
+ * Throughout, a read is taken iff its status is PGN_OK, read_bases[r] <= read_bases[r+1] <= base_capacity and
+ * m = read_bases[r+1] - read_bases[r] > 0.  PGN_DEMUX_NONE = 0xFFFFFFFF stands for "no value".
+ *
+ * pgn_find_patterns_device.  The reads are those pgn_collapse_codes_device or pgn_ctc_decode_device leave (d_seq,
+ * d_read_bases with nreads + 1 entries, d_read_status, base_capacity).  The P = npatterns patterns are device
+ * arrays: d_pat holds their bytes end to end in pat_capacity bytes, pattern p is d_pat[pat_off[p] .. pat_off[p+1])
+ * (d_pat_off has P + 1 entries), d_pat_side[p] is 0 for the head and 1 for the tail, d_max_dist[p] the largest
+ * distance that is a hit.  A pattern is searched iff its side is 0 or 1, pat_off[p] < pat_off[p+1] <= pat_capacity
+ * and its length L = pat_off[p+1] - pat_off[p] <= 128; the arrays are device data, so this check is also what keeps
+ * every access inside d_pat.
+ *   Text      of a taken read for a head pattern: its first n = min(m, window) bases, w0 = 0; for a tail pattern its
+ *             last n bases, w0 = m - n.
+ *   Match     pattern byte x matches text byte y iff x == 'N' or x == y.  Bytes are compared as they are: no case
+ *             folding, and IUPAC codes other than 'N' are plain bytes ('N' in the text matches 'N' in the pattern
+ *             alone).
+ *   Distance  unit costs, the pattern global and the text local: D[0][j] = 0, D[i][0] = i,
+ *               D[i][j] = min(D[i-1][j-1] + !match(p_i, t_j), D[i-1][j] + 1, D[i][j-1] + 1),
+ *             dist = min over j in 0..n of D[L][j], end = w0 + the lowest j that attains it.  So dist <= L, and a
+ *             pattern that matches nowhere gives dist = L and end = w0.
+ *   Start     is computed iff dist <= max_dist[p] (a hit): with the reversed pattern and the text t[0:j] reversed,
+ *             R[0][q] = q, R[i][0] = i and the same recurrence, q* is the lowest q with R[L][q] == dist (it exists),
+ *             and start = end - q*: the shortest span that ends at end, which is the largest start.  Without a hit
+ *             start = PGN_DEMUX_NONE.
+ * d_dist, d_start and d_end are uint32 [nreads, P], a row per read; positions count bases from the read's start
+ * (modulo 2^32).  A read that is not taken, and a pattern that is not searched, get PGN_DEMUX_NONE in all three.
+ * Nothing else is written, and no byte of d_seq outside the taken reads' windows is read.  A workgroup takes one
+ * (read, side) with the window in LDS and a lane per pattern (Myers' bit-vector recurrence, the column in two
+ * 64-bit words); the scratch is 12 bytes per pattern, a per-side index built once per call.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx; window outside 1..PGN_DEMUX_MAX_WINDOW or
+ * npatterns outside 1..PGN_DEMUX_MAX_PATTERNS; nreads >= 2^32; a NULL d_pat_off, d_pat_side or d_max_dist; with
+ * pat_capacity > 0 a NULL d_pat; with nreads > 0 a NULL d_read_bases, d_read_status, d_dist, d_start or d_end; with
+ * base_capacity > 0 a NULL d_seq.  nreads == 0 returns PGN_OK and touches nothing.
+ *
+ * pgn_classify_reads_device.  d_dist, d_start, d_end as the search left them; d_pat_class[p] is a class below
+ * nclasses, or PGN_PATTERN_NO_CLASS for an adapter or primer; any other value is a pattern that never hits.
+ *   A pattern hits a taken read iff its side is 0 or 1 and dist <= max_dist[p] (PGN_DEMUX_NONE is no distance).
+ *   d_c is the lowest dist among the hits of class c, absent without one.  best is the class with the lowest d_c,
+ *   ties to the lowest c; second is the lowest d_c among the other classes.
+ *   barcode[r] = best iff best exists and (second is absent or d_second - d_best >= min_sep), else PGN_DEMUX_NONE.
+ *   The trimming hits are the hits whose class is PGN_PATTERN_NO_CLASS or equals barcode[r].  lo is the largest end
+ *   among the trimming head hits, 0 without one; hi is the smallest start among the trimming tail hits, m without
+ *   one.  If lo >= hi the read stays whole: lo = 0, hi = m.
+ * Outputs, uint32 per read: d_barcode, d_best_dist, d_second_dist (PGN_DEMUX_NONE where absent), d_lo, d_hi.  A read
+ * that is not taken gets PGN_DEMUX_NONE, PGN_DEMUX_NONE, PGN_DEMUX_NONE, 0, 0.  A thread per read; no scratch.
+ * Per-barcode files need nothing more: keep = (barcode == c) is the d_keep of the record writers, and barcode fits
+ * their uint32 tag columns.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx; npatterns outside 1..PGN_DEMUX_MAX_PATTERNS;
+ * nreads >= 2^32; a NULL d_pat_side, d_max_dist or d_pat_class; with nreads > 0 a NULL d_read_bases, d_read_status,
+ * d_dist, d_start, d_end, d_barcode, d_best_dist, d_second_dist, d_lo or d_hi.  nreads == 0 touches nothing.
+ *
+ * pgn_trim_reads_device.  Bases [lo, hi) of every read, with its qualities (d_qual may be NULL) and, when
+ * d_read_frames is not NULL ("with moves"), its move table: d_base_frame as pgn_collapse_codes_device leaves it, and
+ * d_read_frames, d_codes, frame_base and frame_capacity with the meaning they have in pgn_bam_records_device.
+ *   A read is sliced iff it is taken and lo <= hi <= m; with moves its frames [read_frames[r], read_frames[r+1])
+ *   must also lie inside [frame_base, frame_base + frame_capacity), F of them, and with
+ *     f_lo = base_frame[lo] if lo < hi, else 0;  f_hi = base_frame[hi] if lo < hi < m, F if lo < hi == m, else 0
+ *   (base_frame counted from the read's first base) it must hold that f_lo <= f_hi <= F, so no access leaves the
+ *   buffers whatever base_frame holds.  A read that fails has length 0 and keeps its status if that is not PGN_OK,
+ *   else gets PGN_ERR_INVALID_ARG.
+ *   d_new_read_bases (nreads + 1) is the exclusive scan of hi - lo; new base j of read r is old base lo + j, for seq
+ *   and qual.  With moves d_new_read_frames is the scan of f_hi - f_lo, the new codes are the old frames [f_lo,
+ *   f_hi) of the read, new base_frame = old - f_lo, and d_trim_frames[r] = f_lo (0 for a read that is not sliced):
+ *   times the stride, the samples to add to the read's ts.  The first kept base then emits at frame 0, and the kept
+ *   codes hold hi - lo emitting frames when base_frame is that of the codes.
+ *   Both scans always hold the full counts.  A base at or above new_base_capacity and a frame at or above
+ *   new_frame_capacity is not written, and a sliced read with bases or frames there gets PGN_ERR_DST_TOO_SMALL; every
+ *   other sliced read PGN_OK (the rule of pgn_ctc_decode_device).  Nothing else is written.
+ * The lengths, the scan of 1,024-read totals and the offsets as in the record writers; a flat copy over the output
+ * serves seq, qual and codes, a 4-byte form base_frame.  The scratch is 16 bytes per 1,024 reads.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx; nreads >= 2^32; a NULL d_new_read_bases; with
+ * moves a NULL d_new_read_frames; with nreads > 0 a NULL d_read_bases, d_read_status, d_lo, d_hi or d_new_status,
+ * and with moves a NULL d_trim_frames; with base_capacity > 0 a NULL d_seq, and with moves a NULL d_base_frame; with
+ * moves and frame_capacity > 0 a NULL d_codes; with new_base_capacity > 0 a NULL d_new_seq, with d_qual a NULL
+ * d_new_qual, with moves a NULL d_new_base_frame; with moves and new_frame_capacity > 0 a NULL d_new_codes.  With
+ * nreads == 0 only new_read_bases[0] = 0 and, with moves, new_read_frames[0] = 0 are written.
+ *
+ * All three calls are asynchronous on `stream` with no host wait.
+ * Not covered: a BC:Z string tag (barcode goes into a uint32 tag column); two-stage flank-then-barcode scoring and
+ * a both-ends requirement; adapters in the middle of a read and read splitting; affine gaps or scores other than
+ * unit costs; IUPAC classes beyond 'N'; patterns above 128 bytes or windows above 1,024; trimming inside the record
+ * writers; reversed (direct RNA) coordinates, for which the caller swaps the sides; kit definitions: the caller
+ * supplies the sequences. */
+#define PGN_DEMUX_NONE 0xFFFFFFFFu
+#define PGN_PATTERN_NO_CLASS 0xFFFFFFFFu
+#define PGN_DEMUX_MAX_WINDOW 1024u
+#define PGN_DEMUX_MAX_PATTERNS 4096u
+#define PGN_DEMUX_MAX_PATTERN_BYTES 128u
+
+int pgn_find_patterns_device(pgn_ctx *ctx, size_t nreads, const uint8_t *d_seq, const uint64_t *d_read_bases,
+                             const int32_t *d_read_status, uint64_t base_capacity, uint32_t window, uint32_t npatterns,
+                             const uint8_t *d_pat, uint64_t pat_capacity, const uint32_t *d_pat_off,
+                             const uint8_t *d_pat_side, const uint32_t *d_max_dist, uint32_t *d_dist, uint32_t *d_start,
+                             uint32_t *d_end, void *stream);
+
+int pgn_classify_reads_device(pgn_ctx *ctx, size_t nreads, const uint64_t *d_read_bases, const int32_t *d_read_status,
+                              uint64_t base_capacity, uint32_t npatterns, const uint8_t *d_pat_side,
+                              const uint32_t *d_max_dist, const uint32_t *d_pat_class, uint32_t nclasses,
+                              uint32_t min_sep, const uint32_t *d_dist, const uint32_t *d_start, const uint32_t *d_end,
+                              uint32_t *d_barcode, uint32_t *d_best_dist, uint32_t *d_second_dist, uint32_t *d_lo,
+                              uint32_t *d_hi, void *stream);
+
+int pgn_trim_reads_device(pgn_ctx *ctx, size_t nreads, const uint8_t *d_seq, const uint8_t *d_qual /* may be NULL */,
+                          const uint64_t *d_read_bases, const int32_t *d_read_status, uint64_t base_capacity,
+                          const uint32_t *d_lo, const uint32_t *d_hi,
+                          const uint32_t *d_base_frame,
+                          const uint64_t *d_read_frames /* NULL: no moves, and no frame argument is looked at */,
+                          const uint8_t *d_codes, uint64_t frame_base,
+                          uint64_t frame_capacity, uint8_t *d_new_seq, uint8_t *d_new_qual, uint32_t *d_new_base_frame,
+                          uint64_t new_base_capacity, uint64_t *d_new_read_bases, int32_t *d_new_status,
+                          uint8_t *d_new_codes, uint64_t new_frame_capacity, uint64_t *d_new_read_frames,
+                          uint32_t *d_trim_frames, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

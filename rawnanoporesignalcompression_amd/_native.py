@@ -149,6 +149,13 @@ class BamParams(C.Structure):
                 ("d_tag", C.c_void_p * PGN_BAM_MAX_TAGS), ("stride", C.c_uint32), ("pad", C.c_uint32)]
 
 
+PGN_DEMUX_NONE = 0xFFFFFFFF          # no distance, no position, no barcode
+PGN_PATTERN_NO_CLASS = 0xFFFFFFFF    # the class of an adapter or primer
+PGN_DEMUX_MAX_WINDOW = 1024
+PGN_DEMUX_MAX_PATTERNS = 4096
+PGN_DEMUX_MAX_PATTERN_BYTES = 128
+
+
 # pgn_load_kind and pgn_pod5_load_args (include/pgnano_pod5file.h)
 PGN_LOAD_ADC, PGN_LOAD_PA, PGN_LOAD_NORM = 0, 1, 2
 LOAD_KINDS = {"adc": PGN_LOAD_ADC, "pa": PGN_LOAD_PA, "norm": PGN_LOAD_NORM}
@@ -239,6 +246,15 @@ SIGNATURES = [
       _VP, C.c_uint64, _U64P, _I32P, _U64P, _VP]),
     ("pgn_bgzf_deflate_device", C.c_int,
      [_VP, C.c_uint32, _VP, C.c_uint64, _U64P, _VP, C.c_uint64, _U64P, _U64P, _VP]),
+    ("pgn_find_patterns_device", C.c_int,
+     [_VP, _SZ, _VP, _U64P, _I32P, C.c_uint64, C.c_uint32, C.c_uint32, _VP, C.c_uint64, _U32P, _VP, _U32P, _U32P, _U32P,
+      _U32P, _VP]),
+    ("pgn_classify_reads_device", C.c_int,
+     [_VP, _SZ, _U64P, _I32P, C.c_uint64, C.c_uint32, _VP, _U32P, _U32P, C.c_uint32, C.c_uint32, _U32P, _U32P, _U32P,
+      _U32P, _U32P, _U32P, _U32P, _U32P, _VP]),
+    ("pgn_trim_reads_device", C.c_int,
+     [_VP, _SZ, _VP, _VP, _U64P, _I32P, C.c_uint64, _U32P, _U32P, _U32P, _U64P, _VP, C.c_uint64, C.c_uint64, _VP, _VP,
+      _U32P, C.c_uint64, _U64P, _I32P, _VP, C.c_uint64, _U64P, _U32P, _VP]),
     ("pgn_synth_reads_device", C.c_int,
      [_VP, _SZ, C.c_uint64, C.c_uint64, C.c_uint64, _VP, _U64P, _U32P, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
       _VP]),

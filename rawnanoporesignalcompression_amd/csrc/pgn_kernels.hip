@@ -27,6 +27,7 @@
 #include "pgn_fastq.h"
 #include "pgn_bam.h"
 #include "pgn_deflate.h"
+#include "pgn_demux.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -2169,6 +2170,12 @@ struct pgn_ctx {
     // pgn_bgzf_deflate_device: a deflate::BlockPlan per 65,280 stream bytes, written by the plan kernel of every call.
     // PGN_BGZF_KERNELS=plan | scan ends the call behind that kernel (measurements only: no block is written)
     DevBuf<deflate::BlockPlan> bgzfPlans{bufs};
+    // pgn_find_patterns_device: the per-side index of the patterns (the head, tail and not-searched lists and their
+    // counts), built by the first kernel of every call.  pgn_trim_reads_device keeps its workgroups' totals in fqWork
+    DevBuf<uint32_t> demuxIndex{bufs};
+    // PGN_DEMUX_FIND=plain keeps the index in pattern order and both words of the column in every wave
+    // (measurements only: the outputs are the same)
+    bool demuxByLength = true;
     int bgzfKernels = 3;
     bool bamCrcSplit = false;
     uint64_t crfCap = crf::kDefaultScratch;
@@ -2289,6 +2296,7 @@ static int ctx_init(pgn_ctx* c)
     if (const char* v = getenv("PGN_HUF_PRIO_LAST")) c->hufPrioLast = v[0] == '1';
     if (const char* v = getenv("PGN_CRF_TRACEBACK")) c->crfTrace = strcmp(v, "split") == 0 ? 1 : strcmp(v, "none") == 0 ? 2 : 0;
     if (const char* v = getenv("PGN_BAM_CRC")) c->bamCrcSplit = strcmp(v, "split") == 0;
+    if (const char* v = getenv("PGN_DEMUX_FIND")) c->demuxByLength = strcmp(v, "plain") != 0;
     if (const char* v = getenv("PGN_BGZF_KERNELS")) c->bgzfKernels = strcmp(v, "plan") == 0 ? 1 : strcmp(v, "scan") == 0 ? 2 : 3;
     if (const char* v = getenv("PGN_DEFER_TAIL_PLAIN")) { const long x = atol(v); if (x >= 0) c->deferTailPlain = (size_t)x; }
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -4193,6 +4201,211 @@ extern "C" int pgn_bgzf_deflate_device(pgn_ctx* c, uint32_t flags, const uint8_t
     if (c->bgzfKernels < 3) return PGN_OK;
     hipLaunchKernelGGL(deflate::deflate_pack_kernel, dim3(grid), dim3(deflate::kThreads), 0, s, a);
     HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+// ---- adapters and barcodes (pgn_demux.h) -------------------------------------------------------------------------
+extern "C" int pgn_find_patterns_device(pgn_ctx* c, size_t nreads, const uint8_t* d_seq, const uint64_t* d_read_bases,
+                                        const int32_t* d_read_status, uint64_t base_capacity, uint32_t window,
+                                        uint32_t npatterns, const uint8_t* d_pat, uint64_t pat_capacity,
+                                        const uint32_t* d_pat_off, const uint8_t* d_pat_side, const uint32_t* d_max_dist,
+                                        uint32_t* d_dist, uint32_t* d_start, uint32_t* d_end, void* stream)
+{
+    if (!c) return PGN_ERR_INVALID_ARG;
+    if (window < 1 || window > demux::kMaxWindow || npatterns < 1 || npatterns > demux::kMaxPatterns) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    if (!d_pat_off || !d_pat_side || !d_max_dist) return PGN_ERR_INVALID_ARG;
+    if (pat_capacity && !d_pat) return PGN_ERR_INVALID_ARG;
+    if (nreads && (!d_read_bases || !d_read_status || !d_dist || !d_start || !d_end)) return PGN_ERR_INVALID_ARG;
+    if (base_capacity && !d_seq) return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    const int rc = reserve(c, {{c->demuxIndex, (size_t)(3 * npatterns + 3) * sizeof(uint32_t)}});
+    if (rc != PGN_OK) return rc;
+    demux::FindArgs a{};
+    a.nreads = nreads;
+    a.seq = d_seq;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.baseCapacity = base_capacity;
+    a.window = window;
+    a.npat = npatterns;
+    a.pat = d_pat;
+    a.patCapacity = pat_capacity;
+    a.patOff = d_pat_off;
+    a.patSide = d_pat_side;
+    a.maxDist = d_max_dist;
+    a.dist = d_dist;
+    a.start = d_start;
+    a.end = d_end;
+    a.index = c->demuxIndex;
+    a.byLength = c->demuxByLength ? 1u : 0u;
+    hipLaunchKernelGGL(demux::pattern_index_kernel, dim3(1), dim3(demux::kIndexThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    const unsigned grid = (unsigned)std::min<uint64_t>(2 * (uint64_t)nreads, 1u << 22);
+    hipLaunchKernelGGL(demux::find_patterns_kernel, dim3(grid), dim3(demux::kFindThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+extern "C" int pgn_classify_reads_device(pgn_ctx* c, size_t nreads, const uint64_t* d_read_bases,
+                                         const int32_t* d_read_status, uint64_t base_capacity, uint32_t npatterns,
+                                         const uint8_t* d_pat_side, const uint32_t* d_max_dist, const uint32_t* d_pat_class,
+                                         uint32_t nclasses, uint32_t min_sep, const uint32_t* d_dist,
+                                         const uint32_t* d_start, const uint32_t* d_end, uint32_t* d_barcode,
+                                         uint32_t* d_best_dist, uint32_t* d_second_dist, uint32_t* d_lo, uint32_t* d_hi,
+                                         void* stream)
+{
+    if (!c) return PGN_ERR_INVALID_ARG;
+    if (npatterns < 1 || npatterns > demux::kMaxPatterns) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    if (!d_pat_side || !d_max_dist || !d_pat_class) return PGN_ERR_INVALID_ARG;
+    if (nreads && (!d_read_bases || !d_read_status || !d_dist || !d_start || !d_end || !d_barcode || !d_best_dist ||
+                   !d_second_dist || !d_lo || !d_hi))
+        return PGN_ERR_INVALID_ARG;
+    if (nreads == 0) return PGN_OK;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    demux::ClassArgs a{};
+    a.nreads = nreads;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.baseCapacity = base_capacity;
+    a.npat = npatterns;
+    a.nclasses = nclasses;
+    a.minSep = min_sep;
+    a.patSide = d_pat_side;
+    a.maxDist = d_max_dist;
+    a.patClass = d_pat_class;
+    a.dist = d_dist;
+    a.start = d_start;
+    a.end = d_end;
+    a.barcode = d_barcode;
+    a.bestDist = d_best_dist;
+    a.secondDist = d_second_dist;
+    a.lo = d_lo;
+    a.hi = d_hi;
+    const unsigned grid = (unsigned)((nreads + demux::kFlatThreads - 1) / demux::kFlatThreads);
+    hipLaunchKernelGGL(demux::classify_reads_kernel, dim3(grid), dim3(demux::kFlatThreads), 0, sc.s, a);
+    HIPCHK(hipGetLastError());
+    return PGN_OK;
+}
+
+extern "C" int pgn_trim_reads_device(pgn_ctx* c, size_t nreads, const uint8_t* d_seq, const uint8_t* d_qual,
+                                     const uint64_t* d_read_bases, const int32_t* d_read_status, uint64_t base_capacity,
+                                     const uint32_t* d_lo, const uint32_t* d_hi, const uint32_t* d_base_frame,
+                                     const uint64_t* d_read_frames, const uint8_t* d_codes, uint64_t frame_base,
+                                     uint64_t frame_capacity, uint8_t* d_new_seq, uint8_t* d_new_qual,
+                                     uint32_t* d_new_base_frame, uint64_t new_base_capacity, uint64_t* d_new_read_bases,
+                                     int32_t* d_new_status, uint8_t* d_new_codes, uint64_t new_frame_capacity,
+                                     uint64_t* d_new_read_frames, uint32_t* d_trim_frames, void* stream)
+{
+    if (!c) return PGN_ERR_INVALID_ARG;
+    if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    const bool moves = d_read_frames != nullptr;
+    if (!d_new_read_bases) return PGN_ERR_INVALID_ARG;
+    if (moves && !d_new_read_frames) return PGN_ERR_INVALID_ARG;
+    if (nreads) {
+        if (!d_read_bases || !d_read_status || !d_lo || !d_hi || !d_new_status) return PGN_ERR_INVALID_ARG;
+        if (moves && !d_trim_frames) return PGN_ERR_INVALID_ARG;
+    }
+    if (base_capacity && (!d_seq || (moves && !d_base_frame))) return PGN_ERR_INVALID_ARG;
+    if (moves && frame_capacity && !d_codes) return PGN_ERR_INVALID_ARG;
+    if (new_base_capacity && (!d_new_seq || (d_qual && !d_new_qual) || (moves && !d_new_base_frame))) return PGN_ERR_INVALID_ARG;
+    if (moves && new_frame_capacity && !d_new_codes) return PGN_ERR_INVALID_ARG;
+    CallScope sc(c, stream);
+    if (sc.rc) return sc.rc;
+    const hipStream_t s = sc.s;
+    if (nreads == 0) {
+        HIPCHK(hipMemsetAsync(d_new_read_bases, 0, sizeof(uint64_t), s));
+        if (moves) HIPCHK(hipMemsetAsync(d_new_read_frames, 0, sizeof(uint64_t), s));
+        return PGN_OK;
+    }
+    demux::TrimArgs a{};
+    a.nreads = nreads;
+    a.seq = d_seq;
+    a.qual = d_qual;
+    a.readBases = d_read_bases;
+    a.status = d_read_status;
+    a.baseCapacity = base_capacity;
+    a.lo = d_lo;
+    a.hi = d_hi;
+    a.baseFrame = d_base_frame;
+    a.readFrames = d_read_frames;
+    a.codes = d_codes;
+    a.frameBase = frame_base;
+    a.frameCapacity = frame_capacity;
+    a.newSeq = d_new_seq;
+    a.newQual = d_new_qual;
+    a.newBaseFrame = d_new_base_frame;
+    a.newBaseCapacity = new_base_capacity;
+    a.newReadBases = d_new_read_bases;
+    a.newStatus = d_new_status;
+    a.newCodes = d_new_codes;
+    a.newFrameCapacity = new_frame_capacity;
+    a.newReadFrames = d_new_read_frames;
+    a.trimFrames = d_trim_frames;
+    a.nblocks = (nreads + demux::kScanThreads - 1) / demux::kScanThreads;
+    const int rc = reserve(c, {{c->fqWork, (size_t)(2 * (a.nblocks + 1)) * sizeof(uint64_t)}});
+    if (rc != PGN_OK) return rc;
+    a.blockSums = c->fqWork;
+    hipLaunchKernelGGL(demux::trim_len_kernel, dim3((unsigned)a.nblocks), dim3(demux::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < (moves ? 2 : 1); k++) {
+        stitch::PlanArgs top{};  // the scan of the workgroups' totals is the stitch plan's
+        top.blockSums = a.blockSums + k * (a.nblocks + 1);
+        top.nblocks = a.nblocks;
+        hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, top);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(demux::trim_offset_kernel, dim3((unsigned)a.nblocks), dim3(demux::kScanThreads), 0, s, a);
+    HIPCHK(hipGetLastError());
+    // units and values behind the slices' end finish at once, so a capacity far above the kept bases costs little
+    auto flat_grid = [](uint64_t items) {
+        return (unsigned)std::min<uint64_t>((items + demux::kFlatThreads - 1) / demux::kFlatThreads, 1u << 22);
+    };
+    demux::CopyArgs cp{};
+    cp.nreads = nreads;
+    cp.newOff = d_new_read_bases;
+    cp.oldOff = d_read_bases;
+    cp.shift = d_lo;
+    cp.capacity = new_base_capacity;
+    if (new_base_capacity) {
+        const unsigned grid = flat_grid(new_base_capacity / 16 + 2);
+        cp.src = d_seq;
+        cp.dst = d_new_seq;
+        hipLaunchKernelGGL(demux::trim_copy_kernel, dim3(grid), dim3(demux::kFlatThreads), 0, s, cp);
+        HIPCHK(hipGetLastError());
+        if (d_qual) {
+            cp.src = d_qual;
+            cp.dst = d_new_qual;
+            hipLaunchKernelGGL(demux::trim_copy_kernel, dim3(grid), dim3(demux::kFlatThreads), 0, s, cp);
+            HIPCHK(hipGetLastError());
+        }
+        if (moves) {
+            cp.src = d_base_frame;
+            cp.dst = d_new_base_frame;
+            cp.sub = d_trim_frames;
+            hipLaunchKernelGGL(demux::trim_base_frame_kernel, dim3(flat_grid(new_base_capacity)), dim3(demux::kFlatThreads), 0,
+                               s, cp);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (moves && new_frame_capacity) {
+        cp.newOff = d_new_read_frames;
+        cp.oldOff = d_read_frames;
+        cp.oldBase = frame_base;
+        cp.shift = d_trim_frames;
+        cp.sub = nullptr;
+        cp.src = d_codes;
+        cp.dst = d_new_codes;
+        cp.capacity = new_frame_capacity;
+        hipLaunchKernelGGL(demux::trim_copy_kernel, dim3(flat_grid(new_frame_capacity / 16 + 2)), dim3(demux::kFlatThreads), 0,
+                           s, cp);
+        HIPCHK(hipGetLastError());
+    }
     return PGN_OK;
 }
 

@@ -885,3 +885,202 @@ def bgzf_deflate_signal(data, byte_capacity=None):
     kw = len(blocks) if byte_capacity is None else int(np.searchsorted(blk_off, int(byte_capacity), "right")) - 1
     written = np.array([min(len(data), BGZF_BLOCK_BYTES * kw), int(blk_off[kw])], np.uint64)
     return b"".join(blocks[:kw]), blk_off, written
+
+
+# ---- adapters and barcodes: the search, the class of a read and the ragged slice ---------------------------------------
+DEMUX_NONE = _native.PGN_DEMUX_NONE                    # 0xFFFFFFFF: no distance, no position, no barcode
+PATTERN_NO_CLASS = _native.PGN_PATTERN_NO_CLASS        # the class of an adapter or primer
+DEMUX_MAX_WINDOW = _native.PGN_DEMUX_MAX_WINDOW
+DEMUX_MAX_PATTERNS = _native.PGN_DEMUX_MAX_PATTERNS
+DEMUX_MAX_PATTERN_BYTES = _native.PGN_DEMUX_MAX_PATTERN_BYTES
+
+
+def _pattern_columns(patterns, sides, max_dist, classes=None):
+    """``(bytes per pattern, side, max_dist, class)`` as lists of equal length; nothing is refused here, because a
+    model must also say what the device does with a pattern it does not search."""
+    pats = [bytes(p) for p in patterns]
+    cols = [[int(v) for v in np.asarray(c).reshape(-1)] for c in (sides, max_dist)]
+    cols.append([PATTERN_NO_CLASS] * len(pats) if classes is None else [int(v) for v in np.asarray(classes).reshape(-1)])
+    if any(len(c) != len(pats) for c in cols):
+        raise ValueError("sides, max_dist and classes hold one entry per pattern")
+    return pats, cols[0], cols[1], cols[2]
+
+
+def _pattern_last_row(pat, text, anchored):
+    """``D[L][0..n]`` of the unit-cost DP with the pattern global: ``D[0][j] = 0``, or ``j`` when ``anchored``, and
+    ``D[i][0] = i``; pattern byte ``'N'`` matches every text byte, any other byte itself."""
+    n = len(text)
+    at = np.arange(n + 1, dtype=np.int64)
+    row = at.copy() if anchored else np.zeros(n + 1, np.int64)
+    for i, x in enumerate(pat, 1):
+        miss = np.zeros(n, np.int64) if x == 0x4E else (text != x).astype(np.int64)
+        cand = np.concatenate([[i], np.minimum(row[:-1] + miss, row[1:] + 1)])
+        # D[i][j] = min(cand[j], D[i][j-1] + 1) = min over k <= j of cand[k] + (j - k)
+        row = np.minimum.accumulate(cand - at) + at
+    return row
+
+
+def find_patterns_signal(seq, read_bases, status, patterns, sides, max_dist, window=150, base_capacity=None):
+    """Where each pattern fits best in the head or tail window of each read, on the host (include/pgnano_hip.h, the
+    rule of pgn_find_patterns_device).  ``patterns``: byte strings; ``sides``: 0 = head, 1 = tail; ``max_dist``: the
+    largest distance that is a hit.  A read with status 0 and ``m > 0`` bases inside ``base_capacity`` (default
+    ``len(seq)``) is taken; its text is its first ``n = min(m, window)`` bases (``w0 = 0``) for a head pattern, its
+    last ``n`` (``w0 = m - n``) for a tail pattern.  ``dist`` is the least unit-cost edit distance between the whole
+    pattern and any substring of the text (``'N'`` in the pattern matches every byte), ``end`` is ``w0`` plus the
+    lowest text position at which a substring with that distance ends, and for a hit (``dist <= max_dist``) ``start``
+    is the largest start of such a substring that ends there.  Returns ``(dist, start, end)``, uint32 ``[reads,
+    patterns]``; 0xFFFFFFFF in all three for a read that is not taken and for a pattern whose side is not 0 or 1 or
+    whose length is not 1..128, and in ``start`` where there is no hit."""
+    seq = np.asarray(seq, dtype=np.uint8).reshape(-1)
+    W = int(window)
+    if not 1 <= W <= DEMUX_MAX_WINDOW:
+        raise ValueError(f"window must lie in 1..{DEMUX_MAX_WINDOW}")
+    pats, side, md, _ = _pattern_columns(patterns, sides, max_dist)
+    if not 1 <= len(pats) <= DEMUX_MAX_PATTERNS:
+        raise ValueError(f"1..{DEMUX_MAX_PATTERNS} patterns")
+    cap = len(seq) if base_capacity is None else int(base_capacity)
+    ranges = _read_ranges(read_bases, status, cap)
+    out = np.full((3, len(ranges), len(pats)), DEMUX_NONE, np.uint32)
+    searched = [p for p in range(len(pats)) if side[p] in (0, 1) and 1 <= len(pats[p]) <= DEMUX_MAX_PATTERN_BYTES]
+    for r, (b0, m) in enumerate(ranges):
+        if m == 0:
+            continue
+        n = min(m, W)
+        for p in searched:
+            w0 = m - n if side[p] else 0
+            text = seq[b0 + w0:b0 + w0 + n]
+            pat = np.frombuffer(pats[p], np.uint8)
+            last = _pattern_last_row(pat, text, False)
+            dist = int(last.min())
+            j = int(np.argmax(last == dist))           # the lowest j that attains it
+            out[0, r, p], out[2, r, p] = dist, w0 + j
+            if dist <= md[p]:
+                back = _pattern_last_row(pat[::-1], text[:j][::-1], True)
+                out[1, r, p] = w0 + j - int(np.argmax(back == dist))
+    return out[0], out[1], out[2]
+
+
+def classify_signal(dist, start, end, read_bases, status, sides, max_dist, classes, nclasses, min_sep=1,
+                    base_capacity=None):
+    """The barcode of each read and the bases to keep, from the hits of :func:`find_patterns_signal` (include/
+    pgnano_hip.h, the rule of pgn_classify_reads_device).  ``classes``: per pattern a class below ``nclasses``, or
+    :data:`PATTERN_NO_CLASS` for an adapter or primer; any other value never hits.  A pattern hits a taken read iff
+    its side is 0 or 1 and ``dist <= max_dist`` (0xFFFFFFFF is no distance).  ``d_c`` is the lowest distance among
+    the hits of class ``c``; the best class has the lowest ``d_c`` (ties: the lowest class), the second is the lowest
+    ``d_c`` of the others; ``barcode`` is the best class iff there is no second or ``d_second - d_best >= min_sep``.
+    The hits without a class and those of the read's barcode trim: ``lo`` is the largest ``end`` of those at the
+    head (0 without one), ``hi`` the smallest ``start`` of those at the tail (``m`` without one), and ``lo >= hi``
+    leaves the read whole.  Returns ``(barcode, best_dist, second_dist, lo, hi)``, uint32 per read; a read that is
+    not taken gets 0xFFFFFFFF, 0xFFFFFFFF, 0xFFFFFFFF, 0, 0."""
+    dist, start, end = (np.asarray(a).astype(np.uint32) for a in (dist, start, end))
+    P = dist.shape[1] if dist.ndim == 2 else 0
+    _, side, md, cls = _pattern_columns([b""] * P, sides, max_dist, classes)
+    nclasses, min_sep = int(nclasses), int(min_sep)
+    cap = (1 << 64) - 1 if base_capacity is None else int(base_capacity)
+    ranges = _read_ranges(read_bases, status, cap)
+    n = len(ranges)
+    if dist.shape != (n, P) or start.shape != (n, P) or end.shape != (n, P):
+        raise ValueError("dist, start and end are [reads, patterns]")
+    out = np.full((5, n), DEMUX_NONE, np.uint32)
+    out[3:] = 0
+    for r, (_, m) in enumerate(ranges):
+        if m == 0:
+            continue
+        hits = [p for p in range(P) if side[p] in (0, 1) and (cls[p] == PATTERN_NO_CLASS or cls[p] < nclasses)
+                and int(dist[r, p]) != DEMUX_NONE and int(dist[r, p]) <= md[p]]
+        d = {}
+        for p in hits:
+            if cls[p] != PATTERN_NO_CLASS:
+                d[cls[p]] = min(d.get(cls[p], DEMUX_NONE), int(dist[r, p]))
+        order = sorted((v, c) for c, v in d.items())
+        barcode = DEMUX_NONE
+        if order:
+            out[1, r] = order[0][0]
+            if len(order) > 1:
+                out[2, r] = order[1][0]
+            if len(order) == 1 or order[1][0] - order[0][0] >= min_sep:
+                barcode = order[0][1]
+        out[0, r] = barcode
+        trims = [p for p in hits if cls[p] == PATTERN_NO_CLASS or cls[p] == barcode]
+        lo = max([int(end[r, p]) for p in trims if side[p] == 0], default=0)
+        hi = min([int(start[r, p]) for p in trims if side[p] == 1], default=m)
+        if lo >= hi:
+            lo, hi = 0, m
+        out[3, r], out[4, r] = lo, hi
+    return tuple(out)
+
+
+def trim_reads_signal(seq, read_bases, status, lo, hi, qual=None, base_frame=None, moves=None, base_capacity=None,
+                      new_base_capacity=None, new_frame_capacity=None):
+    """Bases ``[lo, hi)`` of every read, with everything the read carries, on the host (include/pgnano_hip.h, the
+    rule of pgn_trim_reads_device).  ``moves``: ``(codes, read_frames, stride[, frame_base])`` as for
+    :func:`bam_records_signal`, together with ``base_frame`` (the frame of each base within its read).  A read is
+    sliced iff it is taken (status 0, ``m > 0`` bases inside ``base_capacity``, default ``len(seq)``) and ``lo <= hi
+    <= m``; with moves its ``F`` frames must also lie inside the window, and ``f_lo = base_frame[lo]`` (0 if ``lo ==
+    hi``) and ``f_hi = base_frame[hi]`` (``F`` if ``hi == m``, 0 if ``lo == hi``) must give ``f_lo <= f_hi <= F``.  A
+    read that fails has length 0 and keeps its status, or gets 10 (PGN_ERR_INVALID_ARG) if that was 0.
+    Returns a dict: ``seq``, ``qual`` (or None), ``read_bases`` (uint64, reads + 1, the scan of ``hi - lo``),
+    ``status``, and with moves ``base_frame`` (the old minus ``f_lo``), ``codes`` (frames ``[f_lo, f_hi)`` of each
+    read), ``read_frames`` (the scan of ``f_hi - f_lo``) and ``trim_frames`` (``f_lo``), else None for the four.
+    Both scans hold the full counts; ``seq``, ``qual`` and ``base_frame`` stop at ``new_base_capacity`` and
+    ``codes`` at ``new_frame_capacity`` (default: nothing is cut), and a read with bases or frames beyond gets
+    status 1 (PGN_ERR_DST_TOO_SMALL)."""
+    seq = np.asarray(seq, dtype=np.uint8).reshape(-1)
+    qual = None if qual is None else np.asarray(qual, dtype=np.uint8).reshape(-1)
+    cap = len(seq) if base_capacity is None else int(base_capacity)
+    ranges = _read_ranges(read_bases, status, cap)
+    n = len(ranges)
+    lo, hi = ([int(v) for v in np.asarray(a).reshape(-1)] for a in (lo, hi))
+    if len(lo) != n or len(hi) != n:
+        raise ValueError("lo and hi hold one entry per read")
+    if moves is not None:
+        if base_frame is None:
+            raise ValueError("moves need base_frame")
+        codes, rf, _, fbase = _bam_moves(moves)
+        codes = np.asarray(codes, dtype=np.uint8).reshape(-1)
+        rf = [int(v) for v in np.asarray(rf).reshape(-1)]
+        if len(rf) != n + 1:
+            raise ValueError("read_frames must hold one entry more than status")
+        bf = np.asarray(base_frame).reshape(-1).astype(np.int64) & 0xFFFFFFFF
+    new_status = np.asarray(status).astype(np.int32).reshape(-1).copy()
+    nrb, nrf, trim = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32)
+    s_parts, q_parts, c_parts, f_parts = [], [], [], []
+    for r, (b0, m) in enumerate(ranges):
+        ok = m > 0 and lo[r] <= hi[r] <= m
+        f_lo = f_hi = 0
+        if ok and moves is not None:
+            f0, f1 = rf[r], rf[r + 1]
+            ok = fbase <= f0 <= f1 <= fbase + len(codes)
+            if ok:
+                F = f1 - f0
+                if lo[r] < hi[r]:
+                    f_lo = int(bf[b0 + lo[r]])
+                    f_hi = int(bf[b0 + hi[r]]) if hi[r] < m else F
+                ok = f_lo <= f_hi <= F
+        if not ok:
+            if new_status[r] == 0:
+                new_status[r] = _native.PGN_ERR_INVALID_ARG
+            nrb[r + 1], nrf[r + 1] = nrb[r], nrf[r]
+            continue
+        a, b = b0 + lo[r], b0 + hi[r]
+        s_parts.append(seq[a:b])
+        if qual is not None:
+            q_parts.append(qual[a:b])
+        nrb[r + 1] = nrb[r] + np.uint64(hi[r] - lo[r])
+        nrf[r + 1] = nrf[r]
+        if moves is not None:
+            f_parts.append((bf[a:b] - f_lo).astype(np.uint32))
+            c_parts.append(codes[f0 - fbase + f_lo:f0 - fbase + f_hi])
+            nrf[r + 1] = nrf[r] + np.uint64(f_hi - f_lo)
+            trim[r] = f_lo
+        short = new_base_capacity is not None and hi[r] > lo[r] and int(nrb[r + 1]) > int(new_base_capacity)
+        short = short or (new_frame_capacity is not None and f_hi > f_lo and int(nrf[r + 1]) > int(new_frame_capacity))
+        new_status[r] = _native.PGN_ERR_DST_TOO_SMALL if short else _native.PGN_OK
+    cat = lambda parts, dtype, limit: np.concatenate(parts + [np.zeros(0, dtype)]).astype(dtype)[:limit]
+    out = {"seq": cat(s_parts, np.uint8, new_base_capacity), "qual": None if qual is None else cat(q_parts, np.uint8, new_base_capacity),
+           "read_bases": nrb, "status": new_status, "base_frame": None, "codes": None, "read_frames": None,
+           "trim_frames": None}
+    if moves is not None:
+        out.update(base_frame=cat(f_parts, np.uint32, new_base_capacity), codes=cat(c_parts, np.uint8, new_frame_capacity),
+                   read_frames=nrf, trim_frames=trim)
+    return out
