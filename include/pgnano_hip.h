@@ -1136,6 +1136,103 @@ int pgn_trim_reads_device(pgn_ctx *ctx, size_t nreads, const uint8_t *d_seq, con
                           uint8_t *d_new_codes, uint64_t new_frame_capacity, uint64_t *d_new_read_frames,
                           uint32_t *d_trim_frames, void *stream);
 
+/* ---- Typed record tags --------------------------------------------------------------------------------------
+ * The two record writers again, with tag columns that have a type: unsigned, signed and float 32-bit values, a
+ * string per read from a dictionary, and a string per read from a pool.
+ *   ... pgn_read_stats_device, pgn_read_qual_device, pgn_classify_reads_device
+ *       -> pgn_bam_records_tagged_device | pgn_fastq_records_tagged_device -> pgn_bgzf_deflate_device
+ * The BAM bytes are those of SAMv1 section 4.2.4, the text that of SAMv1 section 1.5; no outside program defines
+ * the bytes here, so this text does.  Integers and bytes alone: the tolerance is zero.
+ *
+ * pgn_bam_records_tagged_device and pgn_fastq_records_tagged_device take every argument of pgn_bam_records_device
+ * and pgn_fastq_records_device in the same order, with `tags` behind `params`.  params->ntags must be 0: the columns
+ * are those of `tags` alone.  The flags, the stride, the kept-read rule, the layouts (raw and PGN_BAM_BGZF), rec_off,
+ * rec_status, d_written, "no partial records" and "nothing outside the written records is touched" keep the meaning
+ * they have in the old calls.
+ * Per kept read r the columns k = 0 .. ncols - 1 are written in order where the old calls write theirs; in BAM
+ * mv:B:c stays last.  A column has a two-byte name ([A-Za-z][A-Za-z0-9]) and a type:
+ *   PGN_TAG_U32   v = ((const uint32_t *)d_values)[r].  BAM: name0 name1 'I' and the 4 bytes, 7 bytes.
+ *                 FASTQ: '\t' name0 name1 ':' 'i' ':' dec(v), 6 + digits(v) bytes.
+ *   PGN_TAG_I32   v = ((const int32_t *)d_values)[r].  BAM: name0 name1 'i' and the 4 bytes, 7 bytes.
+ *                 FASTQ: the same text with '-' in front of dec(|v|) for v < 0; -2^31 prints as -2147483648.
+ *   PGN_TAG_F32   BAM: name0 name1 'f' and the 4 bytes of d_values exactly as stored, 7 bytes: a NaN's payload and
+ *                 -0 are not touched.  FASTQ: a column of this type refuses the whole call (below); a float's
+ *                 text has no rule here.
+ *   PGN_TAG_DICT  idx = ((const uint32_t *)d_values)[r].  idx >= nstrings: the column is absent for this read, 0
+ *                 bytes in either format, so PGN_DEMUX_NONE leaves an unclassified read untagged and nstrings == 0
+ *                 leaves every read untagged.  Otherwise the span is [d_str_off[idx], d_str_off[idx + 1]).
+ *   PGN_TAG_STR   The span is [d_str_off[r], d_str_off[r + 1]).  The column is always present; an empty span writes
+ *                 an empty value.
+ * A span [a, b) is valid iff a <= b <= str_capacity, b - a <= PGN_TAG_MAX_STRING = 255 and every byte
+ * d_strings[a .. b) is in 0x20 .. 0x7E.  A read that would be kept but has an invalid span in any column is not
+ * kept and gets PGN_ERR_INVALID_ARG, as a read whose frames leave the window does.  A dictionary entry that no kept
+ * read references is never looked at.  No access leaves the buffers, whatever the offsets hold.
+ * A string value (DICT, STR) of len bytes:
+ *   BAM: name0 name1 'Z' the bytes NUL, 4 + len bytes.  FASTQ: '\t' name0 name1 ':' 'Z' ':' the bytes, 6 + len bytes.
+ *   block_size of a kept read = 69 + (m + 1) / 2 + m + sum_k bytes_k(r) + (moves ? 9 + F : 0)
+ *   length of a kept read's FASTQ record = 42 + 2m + sum_k text_k(r)
+ * with bytes_k(r) and text_k(r) the lengths above.
+ *   bam_bound_tagged(nreads, nbases, columns, nframes) = nreads * 74 + nbases + nbases / 2 + sum_k bam_k
+ *                                                         [+ 9 * nreads + nframes]
+ *   fastq_bound_tagged(nreads, nbases, columns) = nreads * 42 + 2 * nbases + sum_k fastq_k
+ * give the host a capacity without a wait, from the column types, each DICT column's longest entry L and each STR
+ * column's pool size: bam_k = 7 * nreads (U32, I32, F32), (4 + L) * nreads (DICT), str_capacity + 4 * nreads (STR);
+ * fastq_k = 16 * nreads (U32), 17 * nreads (I32), (6 + L) * nreads (DICT), str_capacity + 6 * nreads (STR).  A
+ * STR column's term holds for non-decreasing d_str_off; spans that overlap can need more, which rec_off[nreads]
+ * tells as always.
+ * With U32 columns only, every output (the bytes, rec_off, rec_status, d_written) is identical to the old call's
+ * with the same columns.
+ * The length kernels add the columns' bytes, a thread per read, and validate each span they use; the scan and the
+ * offsets are the old calls'; the writers stay flat over the stream, a workgroup per 65,280 stream bytes in BAM and
+ * per PGN_FASTQ_TILE_BYTES in FASTQ, and walk a record's columns where the old ones walk theirs.  The length of a
+ * record's tag area is recomputed in the writer from rec_off (and read_frames), not carried: the scratch is 0
+ * bytes per read and 8 bytes per 1,024 reads, as in the old calls.
+ * PGN_ERR_INVALID_ARG before any GPU call, in this order: a NULL ctx, params or tags; unknown flag bits;
+ * params->ntags != 0; ncols > PGN_REC_MAX_TAGS, or a bad name or an unknown type among the first ncols; in FASTQ a
+ * PGN_TAG_F32 column; with PGN_BAM_MOVES a stride outside 1..127; nreads >= 2^32; a str_capacity >= 2^32; with
+ * nreads > 0 a NULL d_values (types 0 to 3) or a NULL d_str_off (STR, or DICT with nstrings > 0); with
+ * str_capacity > 0 a NULL d_strings; then the old call's remaining conditions in the old call's order (from "with
+ * nreads > 0 a NULL d_read_ids" on, without its d_tag clause).  nreads == 0 writes rec_off[0] = 0 (and d_written =
+ * {0, 0} in BAM) only.  Asynchronous on `stream`, no host wait.
+ *
+ * Not covered: other BAM types (A, c C s S, H, B arrays other than mv); 64-bit values; float text in FASTQ; strings
+ * above 255 bytes; uniqueness of names; a float mean quality computed on the device; @RG header lines, which stay
+ * the caller's header_text; SAM text. */
+#define PGN_TAG_U32  0u   /* BAM 'I'; text  XX:i:dec                                   */
+#define PGN_TAG_I32  1u   /* BAM 'i'; text  XX:i:[-]dec                                */
+#define PGN_TAG_F32  2u   /* BAM 'f', the four bytes as stored; refused in FASTQ       */
+#define PGN_TAG_DICT 3u   /* 'Z': string d_values[r] of a table of nstrings strings    */
+#define PGN_TAG_STR  4u   /* 'Z': string r of a pool with nreads + 1 offsets           */
+#define PGN_REC_MAX_TAGS 16u
+#define PGN_TAG_MAX_STRING 255u
+
+typedef struct pgn_tag_column {
+    uint8_t  name[2];            /* [A-Za-z][A-Za-z0-9] */
+    uint8_t  type, pad;
+    uint32_t nstrings;           /* DICT: entries of the table */
+    const void     *d_values;    /* U32/I32/F32: nreads 4-byte values; DICT: nreads uint32 indices; STR: not read */
+    const uint32_t *d_str_off;   /* DICT: nstrings + 1; STR: nreads + 1 */
+    const uint8_t  *d_strings;
+    uint64_t str_capacity;       /* bytes of d_strings, < 2^32 */
+} pgn_tag_column;
+typedef struct pgn_record_tags { uint32_t ncols, pad; pgn_tag_column col[16]; } pgn_record_tags;
+
+int pgn_bam_records_tagged_device(pgn_ctx *ctx, const pgn_bam_params *params, const pgn_record_tags *tags,
+                                  size_t nreads, const uint8_t *d_read_ids, const uint64_t *d_read_bases,
+                                  const int32_t *d_read_status, const uint8_t *d_keep /* may be NULL */,
+                                  const uint8_t *d_seq, const uint8_t *d_qual /* may be NULL */,
+                                  uint64_t base_capacity, const uint64_t *d_read_frames, const uint8_t *d_codes,
+                                  uint64_t frame_base, uint64_t frame_capacity, uint8_t *d_out,
+                                  uint64_t byte_capacity, uint64_t *d_rec_off, int32_t *d_rec_status,
+                                  uint64_t *d_written, void *stream);
+
+int pgn_fastq_records_tagged_device(pgn_ctx *ctx, const pgn_fastq_params *params, const pgn_record_tags *tags,
+                                    size_t nreads, const uint8_t *d_read_ids, const uint64_t *d_read_bases,
+                                    const int32_t *d_read_status, const uint8_t *d_keep /* may be NULL */,
+                                    const uint8_t *d_seq, const uint8_t *d_qual, uint64_t base_capacity,
+                                    uint8_t *d_out, uint64_t byte_capacity, uint64_t *d_rec_off,
+                                    int32_t *d_rec_status, void *stream);
+
 /* Device generator of the synthetic nanopore-like reads used by bench.py (integer-only, identical
  * to the checker's pgno_synth_read): global read first_read + r * read_stride ->
  * d_samples[d_sample_offsets[r] .. + d_sample_counts[r]). */

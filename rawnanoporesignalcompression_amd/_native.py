@@ -149,6 +149,24 @@ class BamParams(C.Structure):
                 ("d_tag", C.c_void_p * PGN_BAM_MAX_TAGS), ("stride", C.c_uint32), ("pad", C.c_uint32)]
 
 
+# typed record tags: pgn_tag_column, pgn_record_tags
+PGN_TAG_U32, PGN_TAG_I32, PGN_TAG_F32, PGN_TAG_DICT, PGN_TAG_STR = 0, 1, 2, 3, 4
+PGN_REC_MAX_TAGS = 16
+PGN_TAG_MAX_STRING = 255
+
+
+class TagColumn(C.Structure):
+    """pgn_tag_column"""
+    _fields_ = [("name", C.c_uint8 * 2), ("type", C.c_uint8), ("pad", C.c_uint8), ("nstrings", C.c_uint32),
+                ("d_values", C.c_void_p), ("d_str_off", C.c_void_p), ("d_strings", C.c_void_p),
+                ("str_capacity", C.c_uint64)]
+
+
+class RecordTags(C.Structure):
+    """pgn_record_tags"""
+    _fields_ = [("ncols", C.c_uint32), ("pad", C.c_uint32), ("col", TagColumn * PGN_REC_MAX_TAGS)]
+
+
 PGN_DEMUX_NONE = 0xFFFFFFFF          # no distance, no position, no barcode
 PGN_PATTERN_NO_CLASS = 0xFFFFFFFF    # the class of an adapter or primer
 PGN_DEMUX_MAX_WINDOW = 1024
@@ -244,6 +262,12 @@ SIGNATURES = [
     ("pgn_bam_records_device", C.c_int,
      [_VP, C.POINTER(BamParams), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _U64P, _VP, C.c_uint64, C.c_uint64,
       _VP, C.c_uint64, _U64P, _I32P, _U64P, _VP]),
+    ("pgn_bam_records_tagged_device", C.c_int,
+     [_VP, C.POINTER(BamParams), C.POINTER(RecordTags), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _U64P, _VP,
+      C.c_uint64, C.c_uint64, _VP, C.c_uint64, _U64P, _I32P, _U64P, _VP]),
+    ("pgn_fastq_records_tagged_device", C.c_int,
+     [_VP, C.POINTER(FastqParams), C.POINTER(RecordTags), _SZ, _VP, _U64P, _I32P, _VP, _VP, _VP, C.c_uint64, _VP,
+      C.c_uint64, _U64P, _I32P, _VP]),
     ("pgn_bgzf_deflate_device", C.c_int,
      [_VP, C.c_uint32, _VP, C.c_uint64, _U64P, _VP, C.c_uint64, _U64P, _U64P, _VP]),
     ("pgn_find_patterns_device", C.c_int,

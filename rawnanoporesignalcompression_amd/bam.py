@@ -21,9 +21,10 @@ import ctypes as C
 from dataclasses import dataclass
 
 from . import _native
+from . import tags as _tags
 from .codec import DecodedReads, PGNanoCodec, _check, _ptr, _require_device, _require_out
-from .host import (BGZF_EOF, _bam_moves, _fastq_tags, bam_bound, bam_header, bam_records_signal, bgzf_blocks_signal,
-                   bgzf_bound)
+from .host import (BGZF_EOF, _bam_moves, _fastq_tags, bam_bound, bam_bound_tagged, bam_header, bam_records_signal,
+                   bgzf_blocks_signal, bgzf_bound)
 
 __all__ = ["bam_records", "write_bam", "BamRecords", "bam_records_signal", "bgzf_blocks_signal", "bam_bound",
            "bgzf_bound", "bam_header", "BGZF_EOF"]
@@ -54,8 +55,13 @@ def bam_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tags=
     characters, or None for the CTC path's bases (every quality ``0xFF``).  moves: ``(codes, read_frames,
     stride)`` or ``(codes, read_frames, stride, frame_base)``, the per-frame codes :meth:`PGNanoCodec.stitch_rows`
     laid end to end, the reads' frame offsets and the model's stride: the ``mv:B:c`` tag, in signal order whatever
-    ``reverse`` is.  bgzf: frame the stream in blocks of 65,280 bytes with their CRC-32.  out: a one-dimensional
-    uint8 tensor to write into, any alignment (default: a new one of :func:`bam_bound` bytes, through
+    ``reverse`` is.  tags may also hold the typed columns of :mod:`~rawnanoporesignalcompression_amd.tags`
+    (``tags.i32``, ``tags.f32``, ``tags.zdict``, ``tags.zstr``, :func:`demux.barcode_tag
+    <rawnanoporesignalcompression_amd.demux.barcode_tag>`): with one of them among its values the call is
+    pgn_bam_records_tagged_device, :func:`bam_records_tagged_signal
+    <rawnanoporesignalcompression_amd.host.bam_records_tagged_signal>` bit for bit, with at most 16 columns, a plain
+    tensor among them a ``tags.u32``.  bgzf: frame the stream in blocks of 65,280 bytes with their CRC-32.  out: a
+    one-dimensional uint8 tensor to write into, any alignment (default: a new one of :func:`bam_bound` bytes, through
     :func:`bgzf_bound` with ``bgzf``, which always suffices).  No host wait; :meth:`BamRecords.tobytes` is the one."""
     import torch
 
@@ -75,10 +81,12 @@ def bam_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tags=
     _require_device(read_ids, "read_ids", codec.device)
     if read_ids.dtype != torch.uint8 or tuple(read_ids.shape) != (n, 16) or not read_ids.is_contiguous():
         raise ValueError(f"read_ids must be a contiguous uint8 [{n}, 16] tensor")
-    items = list((tags or {}).items())
+    typed = _tags.has_typed(tags)
+    items = [] if typed else list((tags or {}).items())
     _fastq_tags([(name, ()) for name, _ in items], 0)       # the names and their number
     flags = (_native.PGN_BAM_REVERSE if reverse else 0) | (_native.PGN_BAM_BGZF if bgzf else 0)
     prm = _native.BamParams(flags, len(items))
+    columns, typed_cols = _tags.native_columns(codec, tags, n, text=False) if typed else (None, ())
     for k, (name, t) in enumerate(items):
         _require_device(t, f"tags[{name!r}]", codec.device)
         if t.element_size() != 4 or t.is_floating_point() or int(t.numel()) != n or not t.is_contiguous():
@@ -105,6 +113,8 @@ def bam_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tags=
         dev = decoded.seq.device
         if out is None:
             bound = bam_bound(n, capacity, len(items), nframes if moves is not None else None)
+            if typed:
+                bound = bam_bound_tagged(n, capacity, typed_cols, nframes if moves is not None else None)
             out = torch.empty(bgzf_bound(bound) if bgzf else bound, dtype=torch.uint8, device=dev)
         else:
             _require_out(out, "out", codec.device, torch.uint8)
@@ -114,7 +124,12 @@ def bam_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tags=
         status = torch.empty(n, dtype=torch.int32, device=dev)
         written = torch.empty(2, dtype=torch.int64, device=dev)
         nbytes = int(out.numel())
-        _check(codec._lib.pgn_bam_records_device(
+        if typed:
+            tagged = codec._lib.pgn_bam_records_tagged_device
+            call = lambda h, p, *rest: tagged(h, p, C.byref(columns), *rest)
+        else:
+            call = codec._lib.pgn_bam_records_device
+        _check(call(
             codec._h, C.byref(prm), n, _ptr(read_ids) if n else 0, _ptr(decoded.read_bases), _ptr(decoded.status),
             _ptr(keep) if keep is not None and n else 0, _ptr(decoded.seq) if capacity else 0,
             _ptr(qual) if qual is not None and capacity else 0, capacity,

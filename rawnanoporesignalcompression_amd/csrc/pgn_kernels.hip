@@ -28,6 +28,7 @@
 #include "pgn_bam.h"
 #include "pgn_deflate.h"
 #include "pgn_demux.h"
+#include "pgn_tags.h"
 #include "pgn_select.h"
 #include "pgn_vbz.h"
 #include "pgn_variants.h"
@@ -4018,15 +4019,23 @@ extern "C" int pgn_read_qual_device(pgn_ctx* c, const pgn_read_qual_params* para
     return PGN_OK;
 }
 
-extern "C" int pgn_fastq_records_device(pgn_ctx* c, const pgn_fastq_params* params, size_t nreads,
-                                        const uint8_t* d_read_ids, const uint64_t* d_read_bases,
-                                        const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq,
-                                        const uint8_t* d_qual, uint64_t base_capacity, uint8_t* d_out,
-                                        uint64_t byte_capacity, uint64_t* d_rec_off, int32_t* d_rec_status, void* stream)
+// Both FASTQ record calls: `tags` is NULL for pgn_fastq_records_device, whose columns are the params' own, and the
+// typed columns of pgn_fastq_records_tagged_device (pgn_tags.h) otherwise.
+static int fastq_records_call(pgn_ctx* c, const pgn_fastq_params* params, const pgn_record_tags* tags, bool tagged,
+                              size_t nreads, const uint8_t* d_read_ids, const uint64_t* d_read_bases,
+                              const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq,
+                              const uint8_t* d_qual, uint64_t base_capacity, uint8_t* d_out, uint64_t byte_capacity,
+                              uint64_t* d_rec_off, int32_t* d_rec_status, void* stream)
 {
-    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    if (!c || !params || (tagged && !tags)) return PGN_ERR_INVALID_ARG;
+    if (tagged) {
+        if (params->flags & ~(uint32_t)PGN_FASTQ_REVERSE) return PGN_ERR_INVALID_ARG;
+        if (params->ntags != 0) return PGN_ERR_INVALID_ARG;
+        if (!tags::columns_valid(tags, true)) return PGN_ERR_INVALID_ARG;
+    }
     if (!fastq::params_valid(params)) return PGN_ERR_INVALID_ARG;
     if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    if (tagged && !tags::pointers_valid(tags, nreads)) return PGN_ERR_INVALID_ARG;
     if (nreads) {
         if (!d_read_ids || !d_read_bases || !d_read_status || !d_rec_status) return PGN_ERR_INVALID_ARG;
         for (uint32_t k = 0; k < params->ntags; k++)
@@ -4062,35 +4071,78 @@ extern "C" int pgn_fastq_records_device(pgn_ctx* c, const pgn_fastq_params* para
     const int rc = reserve(c, {{c->fqWork, (size_t)(a.nblocks + 2) * sizeof(uint64_t)}});
     if (rc != PGN_OK) return rc;
     a.blockSums = c->fqWork;
-    hipLaunchKernelGGL(fastq::fastq_len_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, a);
+    tags::Cols cols{};
+    if (tagged) {
+        cols.t = *tags;
+        hipLaunchKernelGGL(tags::fastq_len_tagged_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, a, cols);
+    } else {
+        hipLaunchKernelGGL(fastq::fastq_len_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, a);
+    }
     HIPCHK(hipGetLastError());
     stitch::PlanArgs top{};  // the scan of the workgroups' totals is the stitch plan's
     top.blockSums = a.blockSums;
     top.nblocks = a.nblocks;
     hipLaunchKernelGGL(stitch::stitch_scan_kernel, dim3(1), dim3(stitch::kPlanThreads), 0, s, top);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(fastq::fastq_offset_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, a);
+    {
+        // a typed read without a record keeps the status its length kernel wrote: the offset kernel copies
+        // status[r] to rec_status[r] for such a read, so it is given rec_status as the statuses
+        fastq::RecArgs o = a;
+        if (tagged) o.status = d_rec_status;
+        hipLaunchKernelGGL(fastq::fastq_offset_kernel, dim3((unsigned)a.nblocks), dim3(fastq::kScanThreads), 0, s, o);
+    }
     HIPCHK(hipGetLastError());
     if (a.ntiles) {
         // tiles behind the written records end at once, so a capacity far above the text costs little
         const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, 1u << 24);
-        hipLaunchKernelGGL(fastq::fastq_write_kernel, dim3(grid), dim3(fastq::kThreads), 0, s, a);
+        if (tagged)
+            hipLaunchKernelGGL(tags::fastq_write_tagged_kernel, dim3(grid), dim3(fastq::kThreads), 0, s, a, cols);
+        else
+            hipLaunchKernelGGL(fastq::fastq_write_kernel, dim3(grid), dim3(fastq::kThreads), 0, s, a);
         HIPCHK(hipGetLastError());
     }
     return PGN_OK;
 }
 
-// ---- BAM records (pgn_bam.h) ----------------------------------------------------------------------------------
-extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, size_t nreads, const uint8_t* d_read_ids,
-                                      const uint64_t* d_read_bases, const int32_t* d_read_status, const uint8_t* d_keep,
-                                      const uint8_t* d_seq, const uint8_t* d_qual, uint64_t base_capacity,
-                                      const uint64_t* d_read_frames, const uint8_t* d_codes, uint64_t frame_base,
-                                      uint64_t frame_capacity, uint8_t* d_out, uint64_t byte_capacity,
-                                      uint64_t* d_rec_off, int32_t* d_rec_status, uint64_t* d_written, void* stream)
+extern "C" int pgn_fastq_records_device(pgn_ctx* c, const pgn_fastq_params* params, size_t nreads,
+                                        const uint8_t* d_read_ids, const uint64_t* d_read_bases,
+                                        const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq,
+                                        const uint8_t* d_qual, uint64_t base_capacity, uint8_t* d_out,
+                                        uint64_t byte_capacity, uint64_t* d_rec_off, int32_t* d_rec_status, void* stream)
 {
-    if (!c || !params) return PGN_ERR_INVALID_ARG;
+    return fastq_records_call(c, params, nullptr, false, nreads, d_read_ids, d_read_bases, d_read_status, d_keep, d_seq,
+                              d_qual, base_capacity, d_out, byte_capacity, d_rec_off, d_rec_status, stream);
+}
+
+extern "C" int pgn_fastq_records_tagged_device(pgn_ctx* c, const pgn_fastq_params* params, const pgn_record_tags* tags,
+                                               size_t nreads, const uint8_t* d_read_ids, const uint64_t* d_read_bases,
+                                               const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq,
+                                               const uint8_t* d_qual, uint64_t base_capacity, uint8_t* d_out,
+                                               uint64_t byte_capacity, uint64_t* d_rec_off, int32_t* d_rec_status,
+                                               void* stream)
+{
+    return fastq_records_call(c, params, tags, true, nreads, d_read_ids, d_read_bases, d_read_status, d_keep, d_seq,
+                              d_qual, base_capacity, d_out, byte_capacity, d_rec_off, d_rec_status, stream);
+}
+
+// ---- BAM records (pgn_bam.h) ----------------------------------------------------------------------------------
+// Both BAM record calls, as fastq_records_call
+static int bam_records_call(pgn_ctx* c, const pgn_bam_params* params, const pgn_record_tags* tags, bool tagged,
+                            size_t nreads, const uint8_t* d_read_ids, const uint64_t* d_read_bases,
+                            const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq, const uint8_t* d_qual,
+                            uint64_t base_capacity, const uint64_t* d_read_frames, const uint8_t* d_codes,
+                            uint64_t frame_base, uint64_t frame_capacity, uint8_t* d_out, uint64_t byte_capacity,
+                            uint64_t* d_rec_off, int32_t* d_rec_status, uint64_t* d_written, void* stream)
+{
+    if (!c || !params || (tagged && !tags)) return PGN_ERR_INVALID_ARG;
+    if (tagged) {
+        if (params->flags & ~(uint32_t)(PGN_BAM_REVERSE | PGN_BAM_MOVES | PGN_BAM_BGZF)) return PGN_ERR_INVALID_ARG;
+        if (params->ntags != 0) return PGN_ERR_INVALID_ARG;
+        if (!tags::columns_valid(tags, false)) return PGN_ERR_INVALID_ARG;
+    }
     if (!bam::params_valid(params)) return PGN_ERR_INVALID_ARG;
     if ((uint64_t)nreads >> 32) return PGN_ERR_INVALID_ARG;
+    if (tagged && !tags::pointers_valid(tags, nreads)) return PGN_ERR_INVALID_ARG;
     const bool moves = (params->flags & PGN_BAM_MOVES) != 0, bgzf = (params->flags & PGN_BAM_BGZF) != 0;
     if (nreads) {
         if (!d_read_ids || !d_read_bases || !d_read_status || !d_rec_status) return PGN_ERR_INVALID_ARG;
@@ -4135,7 +4187,13 @@ extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, 
     const int rc = reserve(c, {{c->fqWork, (size_t)(a.nblocks + 1) * sizeof(uint64_t)}});
     if (rc != PGN_OK) return rc;
     a.blockSums = c->fqWork;
-    hipLaunchKernelGGL(bam::bam_len_kernel, dim3((unsigned)a.nblocks), dim3(bam::kScanThreads), 0, s, a);
+    tags::Cols cols{};
+    if (tagged) {
+        cols.t = *tags;
+        hipLaunchKernelGGL(tags::bam_len_tagged_kernel, dim3((unsigned)a.nblocks), dim3(bam::kScanThreads), 0, s, a, cols);
+    } else {
+        hipLaunchKernelGGL(bam::bam_len_kernel, dim3((unsigned)a.nblocks), dim3(bam::kScanThreads), 0, s, a);
+    }
     HIPCHK(hipGetLastError());
     stitch::PlanArgs top{};  // the scan of the workgroups' totals is the stitch plan's
     top.blockSums = a.blockSums;
@@ -4147,7 +4205,10 @@ extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, 
     if (a.ntiles) {
         // tiles behind the written records end at once, so a capacity far above the stream costs little
         const unsigned grid = (unsigned)std::min<uint64_t>(a.ntiles, 1u << 24);
-        hipLaunchKernelGGL(bam::bam_write_kernel, dim3(grid), dim3(bam::kThreads), 0, s, a);
+        if (tagged)
+            hipLaunchKernelGGL(tags::bam_write_tagged_kernel, dim3(grid), dim3(bam::kThreads), 0, s, a, cols);
+        else
+            hipLaunchKernelGGL(bam::bam_write_kernel, dim3(grid), dim3(bam::kThreads), 0, s, a);
         HIPCHK(hipGetLastError());
         if (a.crcSplit) {
             hipLaunchKernelGGL(bam::bgzf_crc_kernel, dim3(grid), dim3(bam::kThreads), 0, s, a);
@@ -4155,6 +4216,31 @@ extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, 
         }
     }
     return PGN_OK;
+}
+
+extern "C" int pgn_bam_records_device(pgn_ctx* c, const pgn_bam_params* params, size_t nreads, const uint8_t* d_read_ids,
+                                      const uint64_t* d_read_bases, const int32_t* d_read_status, const uint8_t* d_keep,
+                                      const uint8_t* d_seq, const uint8_t* d_qual, uint64_t base_capacity,
+                                      const uint64_t* d_read_frames, const uint8_t* d_codes, uint64_t frame_base,
+                                      uint64_t frame_capacity, uint8_t* d_out, uint64_t byte_capacity,
+                                      uint64_t* d_rec_off, int32_t* d_rec_status, uint64_t* d_written, void* stream)
+{
+    return bam_records_call(c, params, nullptr, false, nreads, d_read_ids, d_read_bases, d_read_status, d_keep, d_seq,
+                            d_qual, base_capacity, d_read_frames, d_codes, frame_base, frame_capacity, d_out, byte_capacity,
+                            d_rec_off, d_rec_status, d_written, stream);
+}
+
+extern "C" int pgn_bam_records_tagged_device(pgn_ctx* c, const pgn_bam_params* params, const pgn_record_tags* tags,
+                                             size_t nreads, const uint8_t* d_read_ids, const uint64_t* d_read_bases,
+                                             const int32_t* d_read_status, const uint8_t* d_keep, const uint8_t* d_seq,
+                                             const uint8_t* d_qual, uint64_t base_capacity, const uint64_t* d_read_frames,
+                                             const uint8_t* d_codes, uint64_t frame_base, uint64_t frame_capacity,
+                                             uint8_t* d_out, uint64_t byte_capacity, uint64_t* d_rec_off,
+                                             int32_t* d_rec_status, uint64_t* d_written, void* stream)
+{
+    return bam_records_call(c, params, tags, true, nreads, d_read_ids, d_read_bases, d_read_status, d_keep, d_seq, d_qual,
+                            base_capacity, d_read_frames, d_codes, frame_base, frame_capacity, d_out, byte_capacity,
+                            d_rec_off, d_rec_status, d_written, stream);
 }
 
 // ---- BGZF deflate (pgn_deflate.h) -----------------------------------------------------------------------------

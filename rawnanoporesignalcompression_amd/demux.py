@@ -31,7 +31,7 @@ from .codec import DecodedReads, PGNanoCodec, _check, _ptr, _require_device
 from .host import (DEMUX_NONE, PATTERN_NO_CLASS, _bam_moves, classify_signal, find_patterns_signal, trim_reads_signal)
 
 __all__ = ["PatternSet", "barcode_patterns", "adapter_patterns", "revcomp", "find_patterns", "classify", "trim_reads",
-           "PatternHits", "ReadClasses", "TrimmedReads", "find_patterns_signal", "classify_signal", "trim_reads_signal",
+           "barcode_tag", "PatternHits", "ReadClasses", "TrimmedReads", "find_patterns_signal", "classify_signal", "trim_reads_signal",
            "DEMUX_NONE", "PATTERN_NO_CLASS"]
 
 _COMPLEMENT = bytes.maketrans(b"ACGTUNacgtun", b"TGCAANtgcaan")
@@ -249,6 +249,29 @@ def classify(codec: PGNanoCodec, decoded: DecodedReads, hits: PatternHits, patte
                                                                                 (hits.dist, hits.start, hits.end)),
             *(_ptr(t) if n else 0 for t in out), ls.cuda_stream))
     return ReadClasses(*out)
+
+
+def barcode_tag(barcode, names, unclassified=None):
+    """The ``BC:Z`` / ``RG:Z`` column of a record call from :func:`classify`'s ``barcode``: read ``r`` gets
+    ``names[barcode[r]]`` (a :func:`tags.zdict <rawnanoporesignalcompression_amd.tags.zdict>` column, the names
+    uploaded once to the barcodes' device, or a :class:`tags.StringTable` that is there already).  A read without a
+    class (:data:`DEMUX_NONE`, or any index at or above ``len(names)``) gets no tag; with ``unclassified="..."`` it
+    gets that name, an extra entry that a ``torch.where`` on the device maps it to.  No host wait."""
+    import torch
+
+    from . import tags
+
+    if isinstance(names, tags.StringTable):
+        if unclassified is not None:
+            raise ValueError("unclassified needs the names as a list: the extra entry joins their table")
+        return tags.zdict(barcode, names.to(barcode.device))
+    names = [_seq_bytes(s) for s in names]
+    index = barcode
+    if unclassified is not None:
+        none = torch.full_like(barcode, len(names))
+        index = torch.where((barcode < 0) | (barcode >= len(names)), none, barcode)   # uint32 bits: negative is above
+        names = names + [_seq_bytes(unclassified)]
+    return tags.zdict(index, tags.StringTable(names).to(barcode.device))
 
 
 def trim_reads(codec: PGNanoCodec, decoded: DecodedReads, lo, hi, qual=None, moves=None, *, capacity=None,

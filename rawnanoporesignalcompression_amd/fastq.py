@@ -24,8 +24,10 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native
+from . import tags as _tags
 from .codec import DecodedReads, PGNanoCodec, _check, _ptr, _require_device, _require_out
-from .host import _fastq_tags, err_table, fastq_bound, fastq_records_signal, read_qual_params, read_qual_signal
+from .host import (_fastq_tags, err_table, fastq_bound, fastq_bound_tagged, fastq_records_signal, read_qual_params,
+                   read_qual_signal)
 
 __all__ = ["read_qual", "fastq_records", "read_tags", "ReadQual", "FastqRecords", "read_qual_signal",
            "fastq_records_signal", "err_table", "fastq_bound"]
@@ -103,7 +105,11 @@ def fastq_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tag
     decoded and qual as for :func:`read_qual`; ``decoded.seq`` is the second line of a record and ``qual`` the
     fourth.  read_ids: a uint8 ``[reads, 16]`` device tensor, the uuids' bytes.  tags: a dict of two-character name
     to a device tensor of one 32-bit value per read (read as uint32), written as ``\\tXX:i:value`` in insertion
-    order, at most 8.  keep: a uint8 or bool device tensor, a read with 0 gets no record (default: every read with
+    order, at most 8.  With a typed column of :mod:`~rawnanoporesignalcompression_amd.tags` among the values
+    (``tags.i32``, ``tags.zdict``, ``tags.zstr``, :func:`demux.barcode_tag
+    <rawnanoporesignalcompression_amd.demux.barcode_tag>`; ``tags.f32`` is a ``ValueError``, a float has no text
+    rule) the call is pgn_fastq_records_tagged_device, :func:`fastq_records_tagged_signal
+    <rawnanoporesignalcompression_amd.host.fastq_records_tagged_signal>` bit for bit, with at most 16 columns.  keep: a uint8 or bool device tensor, a read with 0 gets no record (default: every read with
     bases does); ``ReadQual.passed`` writes the pass file and its complement the fail file.  reverse: both strings
     backwards.  out: a one-dimensional uint8 tensor to write into, any alignment (default: a new one of
     :func:`fastq_bound` bytes, which always suffices).  No host wait; :meth:`FastqRecords.tobytes` is the one."""
@@ -116,8 +122,10 @@ def fastq_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tag
     _require_device(read_ids, "read_ids", codec.device)
     if read_ids.dtype != torch.uint8 or tuple(read_ids.shape) != (n, 16) or not read_ids.is_contiguous():
         raise ValueError(f"read_ids must be a contiguous uint8 [{n}, 16] tensor")
-    items = list((tags or {}).items())
+    typed = _tags.has_typed(tags)
+    items = [] if typed else list((tags or {}).items())
     _fastq_tags([(name, ()) for name, _ in items], 0)       # the names and their number
+    columns, typed_cols = _tags.native_columns(codec, tags, n, text=True) if typed else (None, ())
     prm = _native.FastqParams(_native.PGN_FASTQ_REVERSE if reverse else 0, len(items))
     for k, (name, t) in enumerate(items):
         _require_device(t, f"tags[{name!r}]", codec.device)
@@ -132,7 +140,8 @@ def fastq_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tag
     with codec._launch(stream) as ls:
         dev = qual.device
         if out is None:
-            out = torch.empty(fastq_bound(n, capacity, len(items)), dtype=torch.uint8, device=dev)
+            bound = fastq_bound_tagged(n, capacity, typed_cols) if typed else fastq_bound(n, capacity, len(items))
+            out = torch.empty(bound, dtype=torch.uint8, device=dev)
         else:
             _require_out(out, "out", codec.device, torch.uint8)
             if out.dim() != 1 or not out.is_contiguous():
@@ -140,7 +149,12 @@ def fastq_records(codec: PGNanoCodec, decoded: DecodedReads, qual, read_ids, tag
         rec_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
         nbytes = int(out.numel())
-        _check(codec._lib.pgn_fastq_records_device(
+        if typed:
+            tagged = codec._lib.pgn_fastq_records_tagged_device
+            call = lambda h, p, *rest: tagged(h, p, C.byref(columns), *rest)
+        else:
+            call = codec._lib.pgn_fastq_records_device
+        _check(call(
             codec._h, C.byref(prm), n, _ptr(read_ids) if n else 0, _ptr(decoded.read_bases), _ptr(decoded.status),
             _ptr(keep) if keep is not None and n else 0, _ptr(decoded.seq) if capacity else 0,
             _ptr(qual) if capacity else 0, capacity, _ptr(out) if nbytes else 0, nbytes, _ptr(rec_off),

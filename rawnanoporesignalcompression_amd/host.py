@@ -539,6 +539,14 @@ def fastq_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=
     rec_status)``: ``rec_off`` (uint64, reads + 1) is the scan of all lengths whatever ``byte_capacity`` is; a
     record that ends above ``byte_capacity`` (default: none does) is left out with status 1
     (PGN_ERR_DST_TOO_SMALL), a read that is not kept has its own status, and ``text`` is the written records."""
+    cols = _fastq_tags(tags, len(np.asarray(status).reshape(-1)))
+    return _fastq_records(read_ids, seq, qual, read_bases, status, keep, reverse, base_capacity, byte_capacity,
+                          lambda r: b"".join(b"\t" + name + b":i:" + str(int(v[r])).encode() for name, v in cols))
+
+
+def _fastq_records(read_ids, seq, qual, read_bases, status, keep, reverse, base_capacity, byte_capacity, tag_text):
+    """The loop of both FASTQ models: ``tag_text(r)`` is the text of read ``r``'s tags, or None for a read that a
+    tag refuses (status 10, no record)."""
     ids = np.asarray(read_ids, dtype=np.uint8).reshape(-1, 16)
     seq, qual = np.asarray(seq, dtype=np.uint8).reshape(-1), np.asarray(qual, dtype=np.uint8).reshape(-1)
     cap = len(seq) if base_capacity is None else int(base_capacity)
@@ -546,7 +554,6 @@ def fastq_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=
     n = len(ranges)
     if len(ids) != n:
         raise ValueError("read_ids must hold 16 bytes per read")
-    cols = _fastq_tags(tags, n)
     keep = None if keep is None else np.asarray(keep).reshape(-1)
     hexd = "0123456789abcdef"
     rec_off, rec_status = np.zeros(n + 1, np.uint64), np.asarray(status).astype(np.int32).reshape(-1).copy()
@@ -555,8 +562,12 @@ def fastq_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=
         if m and (keep is None or keep[r] != 0):
             h = "".join(hexd[b >> 4] + hexd[b & 15] for b in ids[r].tolist())
             rec = bytearray(b"@" + "-".join((h[:8], h[8:12], h[12:16], h[16:20], h[20:])).encode())
-            for name, v in cols:
-                rec += b"\t" + name + b":i:" + str(int(v[r])).encode()
+            text_r = tag_text(r)
+            if text_r is None:
+                rec_status[r] = _native.PGN_ERR_INVALID_ARG
+                rec_off[r + 1] = at
+                continue
+            rec += text_r
             s, q = seq[b0:b0 + m], qual[b0:b0 + m]
             rec += b"\n" + (s[::-1] if reverse else s).tobytes() + b"\n+\n" + (q[::-1] if reverse else q).tobytes() + b"\n"
             fits = byte_capacity is None or at + len(rec) <= int(byte_capacity)
@@ -648,6 +659,17 @@ def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=No
     ``bgzf_blocks_signal(stream)``."""
     import struct
 
+    cols = _fastq_tags(tags, len(np.asarray(status).reshape(-1)))
+    return _bam_records(read_ids, seq, qual, read_bases, status, keep, reverse, moves, base_capacity, byte_capacity, bgzf,
+                        lambda r: b"".join(tname + b"I" + struct.pack("<I", int(v[r])) for tname, v in cols))
+
+
+def _bam_records(read_ids, seq, qual, read_bases, status, keep, reverse, moves, base_capacity, byte_capacity, bgzf,
+                 tag_bytes):
+    """The loop of both BAM models: ``tag_bytes(r)`` is read ``r``'s tags in front of ``mv``, or None for a read
+    that a tag refuses (status 10, no record)."""
+    import struct
+
     ids = np.asarray(read_ids, dtype=np.uint8).reshape(-1, 16)
     seq = np.asarray(seq, dtype=np.uint8).reshape(-1)
     qual = None if qual is None else np.asarray(qual, dtype=np.uint8).reshape(-1)
@@ -656,7 +678,6 @@ def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=No
     n = len(ranges)
     if len(ids) != n:
         raise ValueError("read_ids must hold 16 bytes per read")
-    cols = _fastq_tags(tags, n)
     keep = None if keep is None else np.asarray(keep).reshape(-1)
     if moves is not None:
         codes, rf, stride, fbase = _bam_moves(moves)
@@ -678,6 +699,11 @@ def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=No
                     rec_off[r + 1] = at
                     continue
                 mv = b"mvBc" + struct.pack("<Ib", 1 + f1 - f0, stride) + ((codes[f0 - fbase:f1 - fbase] >> 7) & 1).tobytes()
+            tag_r = tag_bytes(r)
+            if tag_r is None:
+                rec_status[r] = _native.PGN_ERR_INVALID_ARG
+                rec_off[r + 1] = at
+                continue
             h = "".join(hexd[b >> 4] + hexd[b & 15] for b in ids[r].tolist())
             name = "-".join((h[:8], h[8:12], h[12:16], h[16:20], h[20:])).encode() + b"\0"
             s = seq[b0:b0 + m][::-1] if reverse else seq[b0:b0 + m]
@@ -689,9 +715,7 @@ def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=No
                 q = qual[b0:b0 + m][::-1] if reverse else qual[b0:b0 + m]
                 q = (np.clip(q, 33, 126) - 33).astype(np.uint8).tobytes()
             body = struct.pack("<iiBBHHHIiii", -1, -1, 37, 0, 4680, 0, 4, m, -1, -1, 0) + name + packed + q
-            for tname, v in cols:
-                body += tname + b"I" + struct.pack("<I", int(v[r]))
-            body += mv
+            body += tag_r + mv
             rec = struct.pack("<I", len(body)) + body
             fits = limit is None or at + len(rec) <= limit
             rec_status[r] = _native.PGN_OK if fits else _native.PGN_ERR_DST_TOO_SMALL
@@ -703,6 +727,153 @@ def bam_records_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=No
         rec_off[r + 1] = at
     written = np.array([W, bgzf_bound(W) if bgzf else W], np.uint64)
     return b"".join(out), rec_off, rec_status, written
+
+
+# ---- typed record tags (include/pgnano_hip.h, "Typed record tags") --------------------------------------------------
+TAG_U32, TAG_I32, TAG_F32, TAG_DICT, TAG_STR = (_native.PGN_TAG_U32, _native.PGN_TAG_I32, _native.PGN_TAG_F32,
+                                                _native.PGN_TAG_DICT, _native.PGN_TAG_STR)
+REC_MAX_TAGS = _native.PGN_REC_MAX_TAGS
+TAG_MAX_STRING = _native.PGN_TAG_MAX_STRING
+
+
+def _host_array(a, dtype=None):
+    a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    return a if dtype is None else np.ascontiguousarray(a).reshape(-1).view(dtype)
+
+
+class TagColumn:
+    """A typed tag column as the device reads it: ``type`` (TAG_*), ``values`` (one 32-bit entry per read: the
+    value's bits, or a DICT column's index), and for the string types ``str_off`` (uint32 offsets: ``nstrings + 1``
+    for DICT, reads + 1 for STR), ``strings`` (the pool's bytes) and ``str_capacity`` (default: the pool's size).
+    Nothing is checked here: the rule decides per read what an offset means."""
+
+    def __init__(self, type, values=None, str_off=None, strings=None, nstrings=0, str_capacity=None):
+        self.type, self.values, self.str_off, self.strings = int(type), values, str_off, strings
+        self.nstrings = int(nstrings)
+        self.str_capacity = (0 if strings is None else int(len(strings))) if str_capacity is None else int(str_capacity)
+
+    def host(self):
+        """``(values as uint32, str_off as uint32, strings as uint8)``, each a numpy array or None."""
+        v = None if self.values is None else _host_array(self.values, np.uint32)
+        off = None if self.str_off is None else _host_array(self.str_off, np.uint32)
+        pool = None if self.strings is None else _host_array(self.strings, np.uint8)
+        return v, off, pool
+
+    def longest(self):
+        """The longest valid entry of a DICT column's table (what a bound needs); of a table that lies on a device
+        alone, the longest a valid entry can be, so that a bound costs no host wait."""
+        if hasattr(self.str_off, "cpu"):
+            return min(TAG_MAX_STRING, self.str_capacity)
+        _, off, _ = self.host()
+        spans = [int(b) - int(a) for a, b in zip(off[:self.nstrings], off[1:self.nstrings + 1])] if self.nstrings else []
+        return max([s for s in spans if 0 <= s <= TAG_MAX_STRING], default=0)
+
+
+def _tag_columns(tags, nreads):
+    """``[(name bytes, TagColumn)]`` of a tagged record call's tags, checked: names, types and their number; an
+    array that is no :class:`TagColumn` is a U32 column."""
+    items = list(tags.items()) if hasattr(tags, "items") else list(tags or ())
+    if len(items) > REC_MAX_TAGS:
+        raise ValueError(f"at most {REC_MAX_TAGS} typed tags")
+    out = []
+    for name, col in items:
+        name = name.encode("ascii") if isinstance(name, str) else bytes(name)
+        if len(name) != 2 or not (chr(name[0]).isalpha() and chr(name[1]).isalnum()) or max(name) > 127:
+            raise ValueError(f"a tag's name is [A-Za-z][A-Za-z0-9] (got {name!r})")
+        col = getattr(col, "column", col)                   # a wrapper of the tags module
+        if not isinstance(col, TagColumn):
+            col = TagColumn(TAG_U32, _fastq_tags([(name, col)], nreads)[0][1].astype(np.uint32))
+        if not TAG_U32 <= col.type <= TAG_STR:
+            raise ValueError(f"tag {name.decode()}: unknown type {col.type}")
+        if col.type != TAG_STR and (col.values is None or len(_host_array(col.values).reshape(-1)) != nreads):
+            raise ValueError(f"tag {name.decode()} must hold {nreads} values")
+        out.append((name, col))
+    return out
+
+
+def tag_bytes_signal(name, column, r, text=False):
+    """The bytes that typed column ``column`` named ``name`` adds to read ``r``'s record (include/pgnano_hip.h,
+    "Typed record tags"): the BAM tag, or with ``text`` the FASTQ header's ``\\tXX:t:value``.  ``b""`` where a DICT
+    column is absent for the read, None where the read's span is invalid (the read then has no record), and a
+    ``ValueError`` for F32 as text."""
+    import struct
+
+    name = name.encode("ascii") if isinstance(name, str) else bytes(name)
+    v, off, pool = column.host()
+    t = column.type
+    if t in (TAG_U32, TAG_I32, TAG_F32):
+        bits = int(v[r])
+        if t == TAG_F32 and text:
+            raise ValueError("a float tag has no text rule: FASTQ records take no f32 column")
+        if not text:
+            return name + b"Iif"[t:t + 1] + struct.pack("<I", bits)
+        value = bits - (1 << 32) if t == TAG_I32 and bits >> 31 else bits
+        return b"\t" + name + b":i:" + str(value).encode()
+    i = r
+    if t == TAG_DICT:
+        i = int(v[r])
+        if i >= column.nstrings:
+            return b""
+    a, b = int(off[i]), int(off[i + 1])
+    if not (a <= b <= column.str_capacity and b - a <= TAG_MAX_STRING):
+        return None
+    s = pool[a:b].tobytes()
+    if any(ch < 0x20 or ch > 0x7E for ch in s):
+        return None
+    return b"\t" + name + b":Z:" + s if text else name + b"Z" + s + b"\0"
+
+
+def _tag_row(cols, r, text):
+    parts = [tag_bytes_signal(name, col, r, text) for name, col in cols]
+    return None if any(p is None for p in parts) else b"".join(parts)
+
+
+def bam_records_tagged_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=None, reverse=False, moves=None,
+                              base_capacity=None, byte_capacity=None, bgzf=False):
+    """:func:`bam_records_signal` with typed columns (the rule of pgn_bam_records_tagged_device): ``tags`` maps a
+    name to a :class:`TagColumn` (or to plain uint32 values, a U32 column), at most 16.  A kept read with an invalid
+    span in any column has no record and status 10.  Returns what :func:`bam_records_signal` returns."""
+    cols = _tag_columns(tags, len(np.asarray(status).reshape(-1)))
+    return _bam_records(read_ids, seq, qual, read_bases, status, keep, reverse, moves, base_capacity, byte_capacity, bgzf,
+                        lambda r: _tag_row(cols, r, False))
+
+
+def fastq_records_tagged_signal(read_ids, seq, qual, read_bases, status, tags=(), keep=None, reverse=False,
+                                base_capacity=None, byte_capacity=None):
+    """:func:`fastq_records_signal` with typed columns (the rule of pgn_fastq_records_tagged_device); an F32 column
+    is a ``ValueError``.  Returns what :func:`fastq_records_signal` returns."""
+    cols = _tag_columns(tags, len(np.asarray(status).reshape(-1)))
+    if any(col.type == TAG_F32 for _, col in cols):
+        raise ValueError("a float tag has no text rule: FASTQ records take no f32 column")
+    return _fastq_records(read_ids, seq, qual, read_bases, status, keep, reverse, base_capacity, byte_capacity,
+                          lambda r: _tag_row(cols, r, True))
+
+
+def _bound_tagged(nreads, columns, fixed, strz, i32):
+    total = 0
+    for col in (columns.values() if hasattr(columns, "values") else [c[1] if isinstance(c, tuple) else c for c in columns]):
+        col = getattr(col, "column", col)
+        t = col.type if isinstance(col, TagColumn) else TAG_U32
+        if t == TAG_DICT:
+            total += (strz + col.longest()) * nreads
+        elif t == TAG_STR:
+            total += col.str_capacity + strz * nreads
+        else:
+            total += (i32 if t == TAG_I32 else fixed) * nreads
+    return total
+
+
+def bam_bound_tagged(nreads, nbases, columns=(), nframes=None) -> int:
+    """Stream bytes that hold the tagged records: :func:`bam_bound` without tags plus, per column, ``7 * nreads``
+    (U32, I32, F32), ``(4 + longest entry) * nreads`` (DICT) or ``str_capacity + 4 * nreads`` (STR, for
+    non-decreasing offsets)."""
+    return bam_bound(nreads, nbases, 0, nframes) + _bound_tagged(int(nreads), columns, 7, 4, 7)
+
+
+def fastq_bound_tagged(nreads, nbases, columns=()) -> int:
+    """Bytes that hold the tagged FASTQ records: :func:`fastq_bound` without tags plus, per column, ``16 * nreads``
+    (U32), ``17 * nreads`` (I32), ``(6 + longest entry) * nreads`` (DICT) or ``str_capacity + 6 * nreads`` (STR)."""
+    return fastq_bound(nreads, nbases, 0) + _bound_tagged(int(nreads), columns, 16, 6, 17)
 
 
 # ---- BGZF deflate: one Huffman-only dynamic deflate block per BGZF block, or a stored one ---------------------------
